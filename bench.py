@@ -11,13 +11,19 @@ A step  : ONE 60-frame clip, everything included (both all-frames Euler passes, 
           all 120 displacement maps, encoder, 60 x (fused splat + decoder)), frames sharded round-robin
           over the ranks and assembled with ONE RCCL all-gather of the finished clip (the form north_star
           names: --assembly final --encoder redundant, the default) -> "scaling": "strong" (total work fixed).
-          N > 1 also reports `value_rounds_banded`: the same clip with one hidden all-gather per round of frames
+          With --full, N > 1 also reports `value_rounds_banded`: the same clip with one hidden all-gather per round of frames
           and the encoder split into row bands (--assembly rounds --encoder banded), measured after the timed steps.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                  # + everything after the timed steps (below)
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR      # + DIR/frames.npy, DIR/clip_sample.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 3 --warmup 1
 
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs) and prints the line: `roofline`
+comes from events inside the timed steps (traffic from the static file), `parity_err` and `cpu_baseline` are null.  --full adds
+everything measured or checked after the timed steps: parity_err, cpu_baseline, the rocprofv3 counter passes (in-run traffic), the
+context objects below, and N > 1 the other multi-GPU form.
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline     : the fused clip kernel (slr::clip_tile_kernel<G2,false,B4 = true>, csrc/splat_clip.hip; its feature planes plane-blocked by 4: the kernel that does
                  the exp-weighted two-direction splat + normalisation of one frame), timed
@@ -32,7 +38,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   cpu_baseline : the CPU oracle (oracle/, OpenMP over planes) on this box's host cores, same
                  hot path (Euler + 2 x 65-plane splat + normalise) on a sample of frames; plus one thread.
   roofline_dropin / roofline_backward / roofline_conv / roofline_conv_fp32 / c4 / fps_fp32_convs : context measured after the timed
-                 region (N = 1 only).
+                 region (--full, N = 1 only).
 """
 import argparse
 import json
@@ -226,9 +232,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c3", choices=["c3", "c4"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the context measurements after the timed region")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (FETCH_SIZE / WRITE_SIZE of the clip kernel) after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: parity checks, the context measurements, the "
+                         "CPU baseline, the rocprofv3 counter passes, N > 1: the other multi-GPU form (the --no-* options below thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, a fixed sample of the clip, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the context measurements after the timed region")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 counter passes (FETCH_SIZE / WRITE_SIZE of the clip kernel) after the timed steps")
     ap.add_argument("--full-line", action="store_true", help="also put the context objects into the last line (rounds 1-5 format, > 10 KB)")
     ap.add_argument("--assembly", default="final", choices=["rounds", "final"],
                     help="N>1: ONE all-gather of the finished clip (default, the north_star form) | all-gather per round of frames "
@@ -239,6 +250,8 @@ def main():
     ap.add_argument("--encoder", default="redundant", choices=["banded", "redundant"],
                     help="N>1: every rank encodes the image (default) | per-clip encoder in row bands + one all-gather")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -272,10 +285,13 @@ def main():
     step = make_step(model, image, motion, rank, world, a.assembly, a.encoder, frames_u8=u8)
     dt, clip, kev, sev = timed_clips(step, a.steps, a.warmup, world, dev)
     assert clip.shape == ((NFRAMES, H, W, 3) if u8 else (NFRAMES, 3, H, W)) and (u8 or bool(torch.isfinite(clip).all()))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, clip)
+    del clip
 
     c_splat = 65 if a.workload == "c3" else 67              # planes per reference splat call (v1: 67)
     extra, cpu, parity = {}, None, None
-    if world > 1 and (a.assembly, a.encoder) == ("final", "redundant"):
+    if a.full and world > 1 and (a.assembly, a.encoder) == ("final", "redundant"):
         # context beside the contract form: per-round hidden all-gathers + banded encoder (every rank takes part)
         step2 = make_step(model, image, motion, rank, world, "rounds", "banded")
         dt2, clip2, _, _ = timed_clips(step2, max(1, min(a.steps, 3)), 1, world, dev)
@@ -287,9 +303,9 @@ def main():
         my_frames = len(parallel.shard_frames(NFRAMES, rank, world)) * a.steps
         extra["communicator"] = parallel.communicator_report(dev, my_frames, dt)
         assert extra["communicator"]["world_size"] == world == dist.get_world_size()
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         parity = parity_check(model, image, motion, a.workload, dev)
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         try:                                             # context legs never cost the contract line
             extra.update(context_measurements(a.workload, image, motion, dev))
         except Exception as e:
@@ -298,7 +314,7 @@ def main():
             cpu = cpu_baseline(motion.cpu().numpy())
     # HBM bytes of the dominant kernel from counter passes taken NOW, on this box (child processes; the static file is the fallback)
     meas = None
-    if rank == 0 and world == 1 and not a.no_pmc and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_pmc and not a.no_extras:
         try:
             meas = measured_traffic(a.workload)
         except Exception as e:
@@ -352,6 +368,23 @@ def main():
 
 
 # ------------------------------------------------------------------------------------------------ output
+
+DUMP_FRAMES = (0, NFRAMES // 2, NFRAMES - 1)      # whole frames written by --dump-outputs
+DUMP_SAMPLES = 1 << 20                              # + this many values at fixed seeded positions of the whole clip
+
+
+def dump_outputs(out_dir, clip):
+    """What the last timed step returned (the clip, [N,3,H,W] fp32, or [N,H,W,3] uint8 with --frames uint8), as float32 .npy files:
+    frames.npy = the frames DUMP_FRAMES in full (35 MB), clip_sample.npy = DUMP_SAMPLES values at positions drawn once from a fixed
+    seed over the whole clip (sorted, flat index into the clip's layout).  The same arguments give the same inputs, so two builds
+    compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    pos = np.sort(np.random.default_rng(20261016).choice(clip.numel(), DUMP_SAMPLES, replace=False))
+    sample = clip.reshape(-1)[torch.from_numpy(pos).to(clip.device)]
+    frames = clip[list(DUMP_FRAMES)]
+    for name, t in (("frames", frames), ("clip_sample", sample)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
+
 
 def _pick(d, *keys):
     return None if not d else {k: d[k] for k in keys if k in d}

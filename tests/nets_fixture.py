@@ -88,6 +88,35 @@ def net_input_large(net, S=256):
     return torch.from_numpy(x)
 
 
+# tests/test_nets_vs_reference.py (tests/golden/nets_vs_reference.npz, tools/make_golden_reference_checks.py): the reference's
+# networks built from its option parser with the 2-layer flag set, on these inputs.  case: (reference getter, class of
+# slr_sfs_amd.nets and its arguments, state-dict prefix, input shape, input kind)
+VS_REFERENCE = {
+    "encoder_with_z": ("get_encoder", "EncoderWithZ", (), "model.module.encoder.", (1, 3, 24, 40), "image"),
+    "decoder_holes": ("get_decoder", "DecoderPconv2", (64, 3), "model.module.projector.", (1, 64, 32, 48), "holes"),
+    "decoder_all_hole": ("get_decoder", "DecoderPconv2", (64, 3), "", (1, 64, 16, 16), "zeros"),
+    "net_bg": ("get_net_bg", "BGDecoder", (), "", (1, 3, 32, 32), "image"),
+    "alpha_encoder": ("get_alpha_encoder", "Encoder", (3, 2), "", (1, 3, 32, 32), "image"),
+    "alpha_decoder": ("get_alpha_decoder", "DecoderPconv2", (65, 1), "", (1, 65, 32, 32), "band_hole"),
+}
+
+
+def vs_reference_input(case):
+    shape, kind = VS_REFERENCE[case][4:]
+    r = _rng("vs_reference", case, "input")
+    if kind == "image":
+        return torch.from_numpy(r.uniform(-1, 1, shape).astype(np.float32))
+    if kind == "zeros":                                    # everything a hole
+        return torch.zeros(shape)
+    x = r.standard_normal(shape).astype(np.float32)
+    if kind == "holes":                                    # a hole: mask update / ratio / resampling; a single-channel zero
+        x[:, :, 5:20, 10:30] = 0.0
+        x[:, 3, 0, 0] = 0.0
+    else:
+        x[:, :, 8:16, 8:24] = 0.0
+    return torch.from_numpy(x)
+
+
 def digest_positions(tag, size, n=4096):
     return _rng("digest", tag, size).integers(0, size, n)
 

@@ -1100,7 +1100,7 @@ def test_bench_two_ranks_on_one_gpu(form):
     env = dict(os.environ, SLR_BENCH_ONE_GPU_GLOO="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "1", "--warmup", "1", *form], env=env, capture_output=True, text=True,
+                        "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", *form], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1128,6 +1128,39 @@ def test_bench_two_ranks_on_one_gpu(form):
         assert cfg["assembly"] == "rounds" and cfg["encoder"] == "banded"
         assert cfg["collective_bytes_received_per_rank_per_clip"] == 30 * frame + 65 * 768 * 1280 * 4 // 2
         assert "value_rounds_banded" not in d
+
+
+def test_bench_plain_run_and_dump_outputs(S, tmp_path):
+    """A plain bench.py run (no --full): the timed steps and the line only, `steps` as asked, ms_per_step one timed step; with
+    --dump-outputs the last timed step's clip as float32 .npy files within 64 MB, the frames equal to the sampled values."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 60 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["parity_err"] is None and d["cpu_baseline"] is None          # checks and baselines are --full's
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["clip_sample.npy", "frames.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    frames, sample = np.load(out / "frames.npy"), np.load(out / "clip_sample.npy")
+    assert frames.dtype == np.float32 and frames.shape == (3, 3, 768, 1280) and np.isfinite(frames).all()
+    assert sample.dtype == np.float32 and sample.shape == (1 << 20,) and np.isfinite(sample).all()
+    assert np.abs(frames).max() <= 1.0 and frames.std() > 0                 # tanh frames, not a blank buffer
+    pos = np.sort(np.random.default_rng(20261016).choice(60 * 3 * 768 * 1280, 1 << 20, replace=False))    # bench.dump_outputs
+    per_frame = 3 * 768 * 1280
+    for k, t in enumerate((0, 30, 59)):
+        inside = (pos // per_frame) == t
+        assert inside.any() and np.array_equal(sample[inside], frames[k].ravel()[pos[inside] % per_frame])
 
 
 def test_clip_assembler_on_rccl(S, tmp_path):

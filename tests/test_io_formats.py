@@ -23,19 +23,17 @@ def test_flo_roundtrip_and_layout(tmp_path):
     assert m.shape == (1, 2, 5, 7) and np.array_equal(m[0, 0].numpy(), fl[..., 0])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
-def test_flo_matches_reference_reader(tmp_path):
-    """The reference's own read_flo (utils/utils.py:252-261) executed on a file we wrote."""
-    import re
-    src = open("/root/reference/utils/utils.py").read()
-    fn = re.search(r"def read_flo\(strFile\):.*?reshape\(\[ intHeight, intWidth, 2 \]\)", src, re.S).group(0)
-    ns = {"np": np}
-    exec(fn, ns)
+def test_flo_matches_reference_reader(tmp_path, golden_dir):
+    """The reference's own read_flo (utils/utils.py:252-261) executed on a file we wrote: the file's bytes and what that reader
+    returned for them are stored in tests/golden/reference_io.npz (tools/make_golden_reference_checks.py)."""
+    g = np.load(f"{golden_dir}/reference_io.npz")
+    ref_read = g["flo_reference_read"]
     fl = np.random.default_rng(1).standard_normal((4, 9, 2)).astype(np.float32)
     p = str(tmp_path / "b.flo")
     io.write_flo(p, fl)
-    assert np.array_equal(ns["read_flo"](p), fl)
-    assert np.array_equal(io.read_flo(p), ns["read_flo"](p))
+    assert np.array_equal(np.frombuffer(open(p, "rb").read(), np.uint8), g["flo_bytes"])     # the very file the reader was given
+    assert ref_read.dtype == np.float32 and np.array_equal(ref_read, fl)
+    assert np.array_equal(io.read_flo(p), ref_read)
 
 
 def test_plain_pth_motion(tmp_path):

@@ -9,8 +9,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p $out
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1
 (time python -m pytest tests -m gpu -q) > $out/pytest.log 2>&1
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
-python bench.py --workload c4 --no-extras --no-cpu-baseline > $out/bench_c4.json 2> $out/bench_c4.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full --workload c4 --no-extras --no-cpu-baseline > $out/bench_c4.json 2> $out/bench_c4.err
 trace() {   # name, command...
     local name=$1; shift
     mkdir -p $out/$name
@@ -18,8 +18,8 @@ trace() {   # name, command...
     python tools/trace_csv_stats.py $out/$name > $out/${name}_kernel_stats.txt
     rm -rf $out/$name/trace                       # (the raw traces are large; the summaries are what is kept)
 }
-trace bench_default python bench.py --no-cpu-baseline
-trace bench_c3 python bench.py --no-extras --no-cpu-baseline
+trace bench_default python bench.py --full --no-cpu-baseline
+trace bench_c3 python bench.py --full --no-extras --no-cpu-baseline
 trace splat_stage python tools/splat_stage.py 3
 trace splat_stage_v1 python tools/splat_stage.py 3 v1
 trace c2 python tools/c2_bench.py c2

@@ -1,7 +1,7 @@
 """One line per library variant: tile kernel and splat stage of the timed C3 clip (bench.py --no-extras)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"] + sys.argv[1:],
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"] + sys.argv[1:],
                    capture_output=True, text=True)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 if not line:
