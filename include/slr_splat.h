@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 10
+#define SLR_ABI_VERSION 11
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -473,6 +473,39 @@ int slr_upsample_bilinear2x(const float *in, float *out, int N, int C, int H, in
 int slr_conv1x1_small(const float *in, const float *w, const float *bias, float *out,
                       int N, int Cin, int Cout, int H, int W, int in_b8 /* `in` channel-blocked; `out` is always NCHW */,
                       void *stream);
+
+/* ------------------------------------------------------------------ motion U-Nets (ABI 11; csrc/motion.hip)
+ * The networks that predict the motion field from a still image: Unet4Motion (models/networks/architectures.py:382-493, used by
+ * models/unet_motion.py:30-109) and SPADEUnet4MaskMotion (architectures.py:602-743 with SPADE, models/networks/networks.py:422-463, used by
+ * unet_motion.py:111-191).  All their convolutions run on the fp32 rung (v_mfma_f32_32x32x2_f32): the 3x3 ones through
+ * slr_conv3x3_forward with SLR_CONV_F32, the encoder's 4x4 / stride 2 ones through the entry points below.  All tensors NCHW fp32. */
+
+/* Conv2d(Cin, Cout, 4, stride 2, padding 1) (architectures.py:389-396, 612-619):
+ *   out = post(conv4x4s2(pre(in)) + bias),  pre(x) = leaky_relu(x, slope) when `leaky` (the LeakyReLU(0.2) in front of conv2..conv8,
+ *   :448-462), identity otherwise;  post(y) = y * post_scale[c] + post_shift[c] when given (an eval-mode BatchNorm folded to an affine,
+ *   :449-460), identity when both are NULL.  in [N,Cin,H,W], H, W >= 2 -> out [N,Cout,(H-2)/2+1,(W-2)/2+1].  bias [Cout] or NULL.
+ *   Weights are prepared once per layer into fragment order with slr_conv4x4s2_f32_weights (slr_conv4x4s2_weight_bytes bytes). */
+size_t slr_conv4x4s2_weight_bytes(int Cout, int Cin);
+int slr_conv4x4s2_f32_weights(const float *w /* [Cout,Cin,4,4] */, void *wfrag, int Cout, int Cin, void *stream);
+int slr_conv4x4s2_forward(const float *in, const void *wfrag, const float *bias, const float *post_scale, const float *post_shift,
+                          float *out, int N, int Cin, int Cout, int H, int W, int leaky, float slope, void *stream);
+
+/* SPADE with nn.InstanceNorm2d (affine=False, biased variance; networks.py:441-463):
+ *   out = (x - mean) * rsqrt(var + eps) * (1 + gamma) + beta, mean / var per (n, c) plane of x [N,C,H,W];
+ *   gamma_beta [N,2C,H,W]: gamma = channels 0..C-1, beta = channels C..2C-1 (mlp_gamma and mlp_beta as ONE 3x3 convolution). */
+int slr_instnorm_spade(const float *x, const float *gamma_beta, float *out, int N, int C, int H, int W, float eps, void *stream);
+
+/* The segmap of a SPADE layer (networks.py:446-457): F.interpolate(in, size=(H >> k, W >> k)) per channel, bilinear
+ * (align_corners=False) for every channel but `nearest_channel` (the mask: mode='nearest'; -1 = none).  in [N,C,H,W] ->
+ * out [N,C,H>>k,W>>k]; H and W multiples of 2^k. */
+int slr_resize_segmap(const float *in, float *out, int N, int C, int H, int W, int k, int nearest_channel, void *stream);
+
+/* The decoders' x2 up-sampling + skip concatenation: out[n] = cat(up(a[n]), up(b[n])) [N,Ca+Cb,2H,2W] with a [N,Ca,H,W], b [N,Cb,H,W]
+ * (Cb = 0: a alone).  up = nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False) (the expression of
+ * slr_upsample_bilinear2x) except channel `nearest_channel` of EACH source, which is nearest (architectures.py:712-740; -1 = none).
+ * relu = 1: ReLU of the inputs (up(relu(cat)), architectures.py:463-489 and e8 at :710); 2: ReLU of the output (:715-741); 0: none. */
+int slr_upsample2x_concat(const float *a, int Ca, const float *b, int Cb, float *out, int N, int H, int W, int nearest_channel, int relu,
+                          void *stream);
 
 #ifdef __cplusplus
 }

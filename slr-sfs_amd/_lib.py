@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 10
+ABI_VERSION = 11
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # every symbol include/slr_splat.h declares
@@ -27,6 +27,8 @@ SYMBOLS = (
     "slr_conv3x3_forward_skip", "slr_pconv3x3_forward_skip", "slr_conv_pool_ws_bytes", "slr_conv_up_ws_bytes", "slr_conv3x3_forward_skipout", "slr_pconv3x3_forward_skipout",
     "slr_conv1x1_weight_bytes", "slr_conv1x1_split_weights", "slr_conv1x1_f32_weights", "slr_conv1x1_forward",
     "slr_avgpool3x3s2", "slr_upsample_bilinear2x", "slr_conv1x1_small",
+    "slr_conv4x4s2_weight_bytes", "slr_conv4x4s2_f32_weights", "slr_conv4x4s2_forward", "slr_instnorm_spade", "slr_resize_segmap",
+    "slr_upsample2x_concat",
 )
 
 _lib = None
@@ -82,6 +84,8 @@ def lib():
         L.slr_conv_pool_ws_bytes.argtypes = [i, i, i, i]
         L.slr_conv_up_ws_bytes.restype = sz
         L.slr_conv_up_ws_bytes.argtypes = [i, i, i, i]
+        L.slr_conv4x4s2_weight_bytes.restype = sz
+        L.slr_conv4x4s2_weight_bytes.argtypes = [i, i]
         sig = {
             "slr_euler_integrate": [fp, i, i, i, f, fp, fp, vp],
             "slr_euler_integrate_all": [fp, i, i, i, f, fp, fp, vp],
@@ -125,6 +129,11 @@ def lib():
             "slr_avgpool3x3s2": [fp, fp, i, i, i, i, i, vp],
             "slr_upsample_bilinear2x": [fp, fp, i, i, i, i, i, vp],
             "slr_conv1x1_small": [fp, fp, fp, fp, i, i, i, i, i, i, vp],
+            "slr_conv4x4s2_f32_weights": [fp, vp, i, i, vp],
+            "slr_conv4x4s2_forward": [fp, vp, fp, fp, fp, fp, i, i, i, i, i, i, f, vp],
+            "slr_instnorm_spade": [fp, fp, fp, i, i, i, i, f, vp],
+            "slr_resize_segmap": [fp, fp, i, i, i, i, i, i, vp],
+            "slr_upsample2x_concat": [fp, i, fp, i, fp, i, i, i, i, i, vp],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)

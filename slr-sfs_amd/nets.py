@@ -813,3 +813,323 @@ def load_reference_state_dict(net, sd, prefix):
             if blk.conv_b is not None:
                 _load_conv(blk.conv_b, sd, b + "ch_b.0")
     return net
+
+
+# --------------------------------------------------------------------------- motion U-Nets (still image -> motion field)
+# Unet4Motion (models/networks/architectures.py:382-493) and SPADEUnet4MaskMotion (:602-743 with SPADE, models/networks/networks.py:422-463),
+# the motion predictors of models/unet_motion.py:30-191.  On a device every stage is one of this package's kernels and every convolution runs
+# on the fp32 rung (v_mfma_f32_32x32x2_f32): the 4x4 / stride 2 encoder convolutions on slr_conv4x4s2_forward (csrc/motion.hip), the 3x3
+# ones on slr_conv3x3_forward with SLR_CONV_F32 (direct, not Winograd).  The predicted field feeds the Euler integration, which rounds
+# positions at every step: a perturbation of the motion moves whole trajectories, so no reduced-precision rung is offered here.
+MOTION_GRID = 256                        # eight stride-2 halvings: H and W must be multiples of 256 (the reference fails in torch.cat otherwise)
+
+
+def _check_motion_grid(x):
+    H, W = x.shape[-2:]
+    if H % MOTION_GRID or W % MOTION_GRID or H == 0 or W == 0:
+        raise ValueError(f"motion U-Net: H and W must be positive multiples of {MOTION_GRID} (eight stride-2 halvings), got {H} x {W}")
+
+
+class EvalBN(nn.Module):
+    """nn.BatchNorm2d / SyncBatchNorm in eval mode (the 'sync:spectral_batch' norm of the motion U-Net): y = (x - mean) * rsqrt(var + eps) *
+    weight + bias, i.e. the per-channel affine y * scale + shift (folded into the convolution in front of it on the device)."""
+
+    def __init__(self, ch, eps=1e-5):
+        super().__init__()
+        self.eps = eps
+        self.register_buffer("running_mean", torch.zeros(ch))
+        self.register_buffer("running_var", torch.ones(ch))
+        self.register_buffer("weight", torch.ones(ch))
+        self.register_buffer("bias", torch.zeros(ch))
+
+    def scale_shift(self):
+        scale = self.weight / torch.sqrt(self.running_var + self.eps)
+        return scale, self.bias - self.running_mean * scale
+
+    def forward(self, x):
+        return F.batch_norm(x, self.running_mean, self.running_var, self.weight, self.bias, False, 0.0, self.eps)
+
+
+class Conv4x4s2(nn.Module):
+    """nn.Conv2d(cin, cout, 4, stride=2, padding=1) (spectral norm folded into ``weight``), with the LeakyReLU(0.2) in front of it and an
+    eval BatchNorm behind it when asked (architectures.py:448-462): ONE kernel on a device (slr_conv4x4s2_forward)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 4, 4), requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros(cout), requires_grad=False)
+        nn.init.normal_(self.weight, std=math.sqrt(1.0 / (cin * 16)))
+
+    def _frag(self):
+        w = self.weight
+        key = (w.data_ptr(), w._version, w.device)
+        c = self.__dict__.get("_wfrag")
+        if c is None or c[0] != key:
+            L = _lib.lib()
+            buf = torch.empty(L.slr_conv4x4s2_weight_bytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
+            with torch.cuda.device(w.device):
+                _lib.check(L.slr_conv4x4s2_f32_weights(_lib.ptr(w), _lib.ptr(buf), w.shape[0], w.shape[1], _lib.stream_of(w)),
+                           "slr_conv4x4s2_f32_weights")
+            c = self.__dict__["_wfrag"] = (key, buf)
+        return c[1]
+
+    def forward(self, x, leaky=None, bn=None):
+        if _fused_ok(x):
+            N, cin, H, W = x.shape
+            cout = self.weight.shape[0]
+            out = torch.empty(N, cout, (H - 2) // 2 + 1, (W - 2) // 2 + 1, device=x.device, dtype=x.dtype)
+            sc, sh = bn.scale_shift() if bn is not None else (None, None)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.lib().slr_conv4x4s2_forward(_lib.ptr(x), _lib.ptr(self._frag()), _lib.ptr(self.bias), _lib.ptr(sc),
+                                                            _lib.ptr(sh), _lib.ptr(out), N, cin, cout, H, W, int(leaky is not None),
+                                                            float(leaky or 0.0), _lib.stream_of(x)), "slr_conv4x4s2_forward")
+            return out
+        if leaky is not None:
+            x = F.leaky_relu(x, leaky)
+        y = F.conv2d(x, self.weight, self.bias, stride=2, padding=1)
+        return bn(y) if bn is not None else y
+
+
+class BNConv3x3(Conv):
+    """3x3 convolution followed by an eval BatchNorm (or nothing): on a device the BN is folded into the weights and bias of ONE fp32-rung
+    3x3 kernel (prepared once per weight / statistics version); the torch composition runs the two stages as the reference does."""
+
+    def __init__(self, cin, cout, bn=True):
+        super().__init__(cin, cout, 3)
+        self.bn = EvalBN(cout) if bn else None
+
+    def forward(self, x):
+        if self.bn is None:
+            return self.conv(x, self.bias)
+        if not _fused_ok(x):
+            return self.bn(F.conv2d(x, self.weight, self.bias, padding=1))
+        key = (self.weight._version, self.bn.running_var._version, self.bn.running_mean._version, self.bn.weight._version,
+               self.bn.bias._version, self.weight.device)
+        c = self.__dict__.get("_folded")
+        if c is None or c[0] != key:
+            scale, shift = self.bn.scale_shift()
+            folded = Conv(self.cin, self.weight.shape[0], 3).to(self.weight.device)
+            folded.weight.data.copy_(self.weight * scale.view(-1, 1, 1, 1))
+            folded.bias.data.copy_(self.bias * scale + shift)
+            c = self.__dict__["_folded"] = (key, folded)
+        return c[1].conv(x, c[1].bias)
+
+
+def instnorm_spade(x, gamma_beta, eps=1e-5):
+    """SPADE with InstanceNorm2d (networks.py:441-463): instance_norm(x) * (1 + gamma) + beta, gamma_beta = cat(gamma, beta) [N,2C,H,W]."""
+    if _fused_ok(x, gamma_beta):
+        N, C, H, W = x.shape
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().slr_instnorm_spade(_lib.ptr(x), _lib.ptr(gamma_beta), _lib.ptr(out), N, C, H, W, float(eps),
+                                                     _lib.stream_of(x)), "slr_instnorm_spade")
+        return out
+    C = x.shape[1]
+    return F.instance_norm(x, eps=eps) * (1 + gamma_beta[:, :C]) + gamma_beta[:, C:]
+
+
+def resize_segmap(seg, k, nearest_channel=3):
+    """The SPADE segmap at 1 / 2^k of the input's size (networks.py:446-457): bilinear (align_corners=False, size=) for every channel but
+    ``nearest_channel`` (the mask), which is nearest."""
+    if _fused_ok(seg):
+        N, C, H, W = seg.shape
+        out = torch.empty(N, C, H >> k, W >> k, device=seg.device, dtype=seg.dtype)
+        with torch.cuda.device(seg.device):
+            _lib.check(_lib.lib().slr_resize_segmap(_lib.ptr(seg), _lib.ptr(out), N, C, H, W, k, nearest_channel, _lib.stream_of(seg)),
+                       "slr_resize_segmap")
+        return out
+    size = (seg.shape[2] >> k, seg.shape[3] >> k)
+    parts = [F.interpolate(seg[:, :nearest_channel], size=size, mode="bilinear", align_corners=False),
+             F.interpolate(seg[:, nearest_channel:nearest_channel + 1], size=size, mode="nearest")]
+    if seg.shape[1] > nearest_channel + 1:
+        parts.append(F.interpolate(seg[:, nearest_channel + 1:], size=size, mode="bilinear", align_corners=False))
+    return torch.cat(parts, 1)
+
+
+RELU_NONE, RELU_BEFORE, RELU_AFTER = 0, 1, 2
+
+
+def upsample2x_concat(a, b=None, nearest_channel=-1, relu=RELU_NONE):
+    """cat(up(a), up(b)) with up = nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False), except channel ``nearest_channel`` of
+    EACH source, which is nn.Upsample(scale_factor=2, mode='nearest') (architectures.py:710-740); ReLU of the inputs (RELU_BEFORE,
+    Unet4Motion :463-489) or of the result (RELU_AFTER, SPADEUnet4MaskMotion :715-741).  ONE kernel on a device (slr_upsample2x_concat)."""
+    if _fused_ok(a, *([] if b is None else [b])):
+        N, Ca, H, W = a.shape
+        Cb = 0 if b is None else b.shape[1]
+        out = torch.empty(N, Ca + Cb, 2 * H, 2 * W, device=a.device, dtype=a.dtype)
+        with torch.cuda.device(a.device):
+            _lib.check(_lib.lib().slr_upsample2x_concat(_lib.ptr(a), Ca, _lib.ptr(b), Cb, _lib.ptr(out), N, H, W, nearest_channel, relu,
+                                                        _lib.stream_of(a)), "slr_upsample2x_concat")
+        return out
+
+    def up(x):
+        if relu == RELU_BEFORE:
+            x = F.relu(x)
+        if nearest_channel < 0:
+            return F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
+        q = nearest_channel
+        return torch.cat([F.interpolate(x[:, :q], scale_factor=2, mode="bilinear", align_corners=False),
+                          F.interpolate(x[:, q:q + 1], scale_factor=2, mode="nearest"),
+                          F.interpolate(x[:, q + 1:], scale_factor=2, mode="bilinear", align_corners=False)], 1)
+    y = up(a) if b is None else torch.cat([up(a), up(b)], 1)
+    return F.relu(y) if relu == RELU_AFTER else y
+
+
+class SPADEIN(nn.Module):
+    """SPADE(nn.InstanceNorm2d, C, label_nc) (networks.py:422-463).  mlp_gamma and mlp_beta are ONE 3x3 convolution 128 -> 2C
+    (``mlp_gb``: gamma's weights, then beta's), the ReLU of mlp_shared is that convolution's prologue; ``seg`` is the segmap already
+    resized to x's size (resize_segmap)."""
+
+    def __init__(self, C, label_nc=6, nhidden=128):
+        super().__init__()
+        self.C = C
+        self.mlp_shared = Conv(label_nc, nhidden, 3)
+        self.mlp_gb = Conv(nhidden, 2 * C, 3)
+        self.register_buffer("_ones", torch.ones(nhidden), persistent=False)
+        self.register_buffer("_zeros", torch.zeros(nhidden), persistent=False)
+
+    def forward(self, x, seg):
+        if _fused_ok(x, seg):
+            actv = self.mlp_shared.conv(seg, self.mlp_shared.bias)
+            gb = self.mlp_gb.conv(actv, self.mlp_gb.bias, pre_bn=(self._ones, self._zeros))     # relu(actv * 1 - 0)
+        else:
+            gb = F.conv2d(F.relu(F.conv2d(seg, self.mlp_shared.weight, self.mlp_shared.bias, padding=1)), self.mlp_gb.weight,
+                          self.mlp_gb.bias, padding=1)
+        return instnorm_spade(x, gb)
+
+
+# per level: the suffix of the reference's norm layer (batch_norm<suffix> / spade_layer<suffix>, architectures.py:423-436, 683-695) after
+# encoder conv_i (i = 2..7) and decoder dconv_k (k = 1..7)
+_MOTION_ENC_NORM = {2: "2_0", 3: "4_0", 4: "8_0", 5: "8_1", 6: "8_2", 7: "8_3"}
+_MOTION_DEC_NORM = {1: "8_4", 2: "8_5", 3: "8_6", 4: "8_7", 5: "4_1", 6: "2_1", 7: ""}
+
+
+class _MotionUnet(nn.Module):
+    """The layers both motion U-Nets share (architectures.py:389-410, 612-633): conv1..conv8 4x4 / stride 2 (nf, 2nf, 4nf, 8nf x 5 output
+    channels), dconv1..dconv8 3x3 (the last one onto ``cout`` channels)."""
+
+    def __init__(self, cin, cout, nf, bn):
+        super().__init__()
+        self.cin = cin
+        enc = [cin, nf, nf * 2, nf * 4, nf * 8, nf * 8, nf * 8, nf * 8, nf * 8]
+        for i in range(1, 9):
+            setattr(self, f"conv{i}", Conv4x4s2(enc[i - 1], enc[i]))
+        dec = [(nf * 8, nf * 8), (nf * 16, nf * 8), (nf * 16, nf * 8), (nf * 16, nf * 8), (nf * 16, nf * 4), (nf * 8, nf * 2),
+               (nf * 4, nf), (nf * 2, cout)]
+        for k, (ci, co) in enumerate(dec, 1):
+            setattr(self, f"dconv{k}", BNConv3x3(ci, co, bn=bn and k < 8))
+
+    def _check_input(self, x):
+        _check_motion_grid(x)
+        if x.dim() != 4 or x.shape[1] != self.cin:
+            raise ValueError(f"{type(self).__name__}: input [N, {self.cin}, H, W] expected, got {tuple(x.shape)}")
+
+
+class Unet4Motion(_MotionUnet):
+    """Unet4Motion (architectures.py:382-493) in eval mode with BatchNorm (norm_G 'sync:spectral_batch'): e1 = conv1(x),
+    e_i = bn(conv_i(leaky_relu(e_{i-1}, 0.2))) for i = 2..7, e8 = conv8(leaky_relu(e7)); decoder
+    d_k = bn(dconv_k(up(relu(cat(d_{k-1}, e_{9-k}))))) with all-bilinear x2 up-sampling (align_corners=False), out = dconv8(...) (no BN).
+    The encoder's BNs ride in the 4x4 kernel's epilogue, the decoder's are folded into the 3x3 weights.  H, W multiples of 256."""
+
+    def __init__(self, cin=3, cout=2, nf=32):
+        super().__init__(cin, cout, nf, bn=True)
+        for i, s in _MOTION_ENC_NORM.items():
+            setattr(self, f"bn{s}", EvalBN(getattr(self, f"conv{i}").weight.shape[0]))
+
+    @torch.no_grad()
+    def forward(self, x):
+        self._check_input(x)
+        with fp32_kernels(winograd=False):
+            e = [self.conv1(x)]
+            for i in range(2, 9):
+                e.append(getattr(self, f"conv{i}")(e[-1], leaky=0.2, bn=getattr(self, f"bn{_MOTION_ENC_NORM[i]}") if i < 8 else None))
+            d = upsample2x_concat(e[7], None, -1, RELU_BEFORE)                       # up(relu(e8))
+            for k in range(1, 8):
+                d = upsample2x_concat(getattr(self, f"dconv{k}")(d), e[7 - k], -1, RELU_BEFORE)
+            return self.dconv8(d)
+
+
+class SPADEUnet4MaskMotion(_MotionUnet):
+    """SPADEUnet4MaskMotion (architectures.py:602-743) with SPADE(InstanceNorm2d, C, 6) after conv2..conv7 and dconv1..dconv7, conditioned on
+    the network input (RGB, mask, hint) resized to each level (mask nearest).  Decoder quirks reproduced: every x2 up-sampling is bilinear
+    except channel 3 of each up-sampled tensor (nearest), feature map and skip alike; ReLU after up-sampling + concatenation, except for e8
+    (ReLU first, :709-710).  The segmap branch needs the 6-channel input (mask + hint): with 3 channels the reference's SPADE does not resize
+    its segmap, with 4 its mlp_shared (6 input channels) does not match -- both fail there, and raise here.  H, W multiples of 256."""
+
+    def __init__(self, cin=6, cout=2, nf=32):
+        if cin != 6:
+            raise ValueError(f"SPADEUnet4MaskMotion: the SPADE segmap is the 6-channel input (RGB, mask, hint); got {cin} channels "
+                             "(the reference fails for these too: its mlp_shared takes 6)")
+        super().__init__(cin, cout, nf, bn=False)
+        for i, s in _MOTION_ENC_NORM.items():
+            setattr(self, f"spade_layer{s}", SPADEIN(getattr(self, f"conv{i}").weight.shape[0]))
+        for k, s in _MOTION_DEC_NORM.items():
+            setattr(self, f"spade_layer{s}", SPADEIN(getattr(self, f"dconv{k}").weight.shape[0]))
+
+    @torch.no_grad()
+    def forward(self, x):
+        self._check_input(x)
+        with fp32_kernels(winograd=False):
+            seg = {k: resize_segmap(x, k) for k in range(1, 8)}                   # once per prediction, every level
+            e = [self.conv1(x)]
+            for i in range(2, 8):
+                y = getattr(self, f"conv{i}")(e[-1], leaky=0.2)
+                e.append(getattr(self, f"spade_layer{_MOTION_ENC_NORM[i]}")(y, seg[i]))
+            e.append(self.conv8(e[-1], leaky=0.2))
+            d = upsample2x_concat(e[7], None, 3, RELU_BEFORE)                        # relu(e8), then the mixed up-sampling
+            for k in range(1, 8):
+                d_ = getattr(self, f"spade_layer{_MOTION_DEC_NORM[k]}")(getattr(self, f"dconv{k}")(d), seg[8 - k])
+                d = upsample2x_concat(d_, e[7 - k], 3, RELU_AFTER)
+            return self.dconv8(d)
+
+
+def _take(sd, used, key):
+    used.add(key)
+    return sd[key]
+
+
+@torch.no_grad()
+def load_motion_state_dict(net, sd, prefix):
+    """Fill a motion U-Net from the reference's state dict of Unet4Motion / SPADEUnet4MaskMotion under ``prefix``
+    ('model.module.motion_regressor.motion_predictor.' in an animating checkpoint trained with --train_motion,
+    'model.module.motion_predictor.' in a motion checkpoint of train_motion_unet.py).  Spectral norm is folded at load (weight_orig /
+    (u^T W v), no power iteration: its eval mode).  Every key under the prefix must be consumed, and every parameter found."""
+    sub = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    if not sub:
+        raise KeyError(f"no key of the state dict starts with {prefix!r}")
+    used = set()
+
+    def conv(mod, key):
+        w = _fold_sn(sub, key)
+        used.update(k for k in (key + ".weight", key + ".weight_orig", key + ".weight_u", key + ".weight_v") if k in sub)
+        if tuple(w.shape) != tuple(mod.weight.shape):
+            raise ValueError(f"{prefix}{key}: weight {tuple(w.shape)}, the network expects {tuple(mod.weight.shape)}")
+        mod.weight.data.copy_(w)
+        mod.bias.data.copy_(_take(sub, used, key + ".bias"))
+
+    def bn(mod, key):
+        for name in ("running_mean", "running_var", "weight", "bias"):
+            getattr(mod, name).copy_(_take(sub, used, f"{key}.{name}"))
+        if key + ".num_batches_tracked" in sub:
+            used.add(key + ".num_batches_tracked")
+
+    for i in range(1, 9):
+        conv(getattr(net, f"conv{i}"), f"conv{i}")
+        conv(getattr(net, f"dconv{i}"), f"dconv{i}")
+    if isinstance(net, Unet4Motion):
+        for s in _MOTION_ENC_NORM.values():
+            bn(getattr(net, f"bn{s}"), f"batch_norm{s}")
+        for k, s in _MOTION_DEC_NORM.items():
+            bn(getattr(net, f"dconv{k}").bn, f"batch_norm{s}")
+    else:
+        for s in list(_MOTION_ENC_NORM.values()) + list(_MOTION_DEC_NORM.values()):
+            sp = getattr(net, f"spade_layer{s}")
+            key = f"spade_layer{s}"
+            sp.mlp_shared.weight.data.copy_(_take(sub, used, key + ".mlp_shared.0.weight"))
+            sp.mlp_shared.bias.data.copy_(_take(sub, used, key + ".mlp_shared.0.bias"))
+            sp.mlp_gb.weight.data.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.weight"), _take(sub, used, key + ".mlp_beta.weight")]))
+            sp.mlp_gb.bias.data.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.bias"), _take(sub, used, key + ".mlp_beta.bias")]))
+    left = sorted(set(sub) - used)
+    if left:
+        raise KeyError(f"motion U-Net: {len(left)} key(s) under {prefix!r} not consumed (another norm / architecture?): {left[:6]}")
+    return net

@@ -280,15 +280,37 @@ def splat_options(opts, two_layer):
     return kw
 
 
-class BaselineAnimator(torch.nn.Module, _ConvRung):
-    def __init__(self, encoder=None, decoder=None, clamp_z=None, softmax_v1=False, softmax_v2=False, opts=None, convs="auto"):
+class _MotionSource:
+    """The motion of a clip: given (px / frame on the working grid), or predicted from the image by the animator's ``motion_regressor``
+    (motion.MotionRegressor) -- what the reference's forward_flow does when the batch has no "motions" (animating_softmax_splating.py:834-840,
+    ..._2layers_alpha_seperate.py:909-914).  Predicted once per clip, before the Euler pass; under ``shard`` every rank predicts it
+    (redundantly, like the encoder's frame-invariant work)."""
+
+    def _motion(self, image, motion, motion_mask=None, motion_hint=None):
+        if motion is not None:
+            return motion
+        if self.motion_regressor is None:
+            raise ValueError(f"{type(self).__name__}: no motion given and no motion_regressor to predict one")
+        return self.motion_regressor.forward_flow(image, motion_mask, motion_hint)["PredMotion"].contiguous()
+
+    def _batch_motion(self, batch):
+        if "motions" in batch:
+            return batch["motions"][0]
+        return self._motion(batch["images"][0], None, batch.get("motion_mask"), batch.get("motion_hint"))
+
+
+class BaselineAnimator(torch.nn.Module, _ConvRung, _MotionSource):
+    def __init__(self, encoder=None, decoder=None, clamp_z=None, softmax_v1=False, softmax_v2=False, opts=None, convs="auto",
+                 motion_regressor=None):
         """clamp_z / softmax_v1 / softmax_v2: see ClipSynthesizer; ``opts`` (the checkpoint's pickled Namespace)
         sets them the way the reference's forward_flow reads them (splat_options).  convs: arithmetic of the encoder /
         decoder convolutions, one of CONV_POLICIES (see _render): "auto" = split-f16 matrix-core kernels with an automatic
-        step up (activation scale 1, then the package's fp32 matrix-core kernels) where an activation leaves their exact range."""
+        step up (activation scale 1, then the package's fp32 matrix-core kernels) where an activation leaves their exact range.
+        motion_regressor: optional motion.MotionRegressor -- clips given no motion get the one it predicts from the image."""
         super().__init__()
         assert convs in CONV_POLICIES
         self.convs, self._conv_rung = convs, 0
+        self.motion_regressor = motion_regressor
         self.encoder = encoder if encoder is not None else nets.EncoderWithZ()
         self.projector = decoder if decoder is not None else nets.DecoderPconv2(64, 3)
         self.splat_kw = dict(clamp_z=clamp_z, softmax_v1=softmax_v1, softmax_v2=softmax_v2)
@@ -296,10 +318,12 @@ class BaselineAnimator(torch.nn.Module, _ConvRung):
             self.splat_kw = splat_options(opts, two_layer=False)
 
     @torch.no_grad()
-    def begin_clip(self, image, motion, N, shard=None, frames=None, convs=None):
-        """Frame-invariant part.  image [1,3,H,W] in [-1,1]; motion [1,2,H,W] px/frame.
+    def begin_clip(self, image, motion, N, shard=None, frames=None, convs=None, motion_mask=None, motion_hint=None):
+        """Frame-invariant part.  image [1,3,H,W] in [-1,1]; motion [1,2,H,W] px/frame, or None: predicted by the motion regressor
+        (with motion_mask / motion_hint when it takes them, motion.motion_inputs_from_flow).
         shard = (rank, world[, group]): the encoder runs in row bands across the ranks (parallel.encode_banded).
         frames: the frames that will be rendered (default all): bins / work plans are prepared for those."""
+        motion = self._motion(image, motion, motion_mask, motion_hint)
         plan = MotionPlan(motion, N, frames)                        # motion-only work first (its totals reach the host
         fs, Z = _encode(self.encoder, image, shard, convs or self.convs, self)   # under the encoder); start_fs, Z_f (:779-786)
         return ClipSynthesizer(fs, Z, motion, N, plan=plan, **self.splat_kw)
@@ -315,22 +339,23 @@ class BaselineAnimator(torch.nn.Module, _ConvRung):
         Re-does the per-clip work on every call, like the reference; use begin_clip/frame for speed."""
         start, middle, end = [int(v) for v in torch.as_tensor(batch["index"]).reshape(-1)[:3]]
         fs, Z = batch["features"][0][:2]
-        clip = ClipSynthesizer(fs, Z.view(fs.shape[0], 1, fs.shape[2], fs.shape[3]), batch["motions"][0],
+        clip = ClipSynthesizer(fs, Z.view(fs.shape[0], 1, fs.shape[2], fs.shape[3]), self._batch_motion(batch),
                                end - start + 1, frames=[middle - start], **self.splat_kw)
         gen = clip.features(middle - start)
         return {"PredImg": torch.tanh(self.projector(gen)), "Z_f": Z}
 
     @torch.no_grad()
-    def synthesize(self, image, motion, N, frames=None, overlap=False, on_frame=None, shard=None, batch=None, convs=None):
+    def synthesize(self, image, motion, N, frames=None, overlap=False, on_frame=None, shard=None, batch=None, convs=None,
+                   motion_mask=None, motion_hint=None):
         """All (or the given) frames of one clip -> [len(frames),3,H,W] on the device.  batch (default DECODE_BATCH):
         frames per decoder launch; overlap=True (see _features_ahead) decodes frame by frame; convs: overrides the
-        animator's convolution policy for this clip (CONV_POLICIES)."""
+        animator's convolution policy for this clip (CONV_POLICIES).  motion None: predicted (begin_clip)."""
         _check_grid(image)
         frames = list(range(N) if frames is None else frames)
         policy = self.convs if convs is None else convs
         assert policy in CONV_POLICIES
         self._clip_begins()
-        clip = self.begin_clip(image, motion, N, shard, frames, convs=policy)
+        clip = self.begin_clip(image, motion, N, shard, frames, convs=policy, motion_mask=motion_mask, motion_hint=motion_hint)
         out = image.new_empty(len(frames), 3, image.shape[2], image.shape[3])
         batch = DECODE_BATCH if batch is None else max(1, int(batch))
 
@@ -362,12 +387,12 @@ def blur_alpha_region(alpha_region, W):
     return torch.nn.functional.conv2d(x, g)
 
 
-class SLRv1Animator(torch.nn.Module, _ConvRung):
+class SLRv1Animator(torch.nn.Module, _ConvRung, _MotionSource):
     KEYS = ("PredImg", "BGImg", "FluidImg", "CompositeFluidAlpha")
 
     def __init__(self, encoder=None, decoder=None, net_bg=None, alpha_encoder=None, alpha_decoder=None,
                  use_alpha0=True, softmax_v1=False, softmax_v2=False, use_alpha_softmax=False, clamp_alpha=0.0,
-                 use_fluid_alpha_only=False, use_bg_alpha_only=False, opts=None, convs="auto"):
+                 use_fluid_alpha_only=False, use_bg_alpha_only=False, opts=None, convs="auto", motion_regressor=None):
         """Compositing options of ..._2layers_alpha_seperate.py:1060-1085 (all off in the shipped scripts):
         use_alpha_softmax, clamp_alpha (> 0: lower bound of the composited fluid alpha -- not the clamp of the time
         weight, which this model always applies, :952), use_fluid_alpha_only, use_bg_alpha_only.  ``opts`` (the
@@ -375,6 +400,7 @@ class SLRv1Animator(torch.nn.Module, _ConvRung):
         super().__init__()
         assert convs in CONV_POLICIES
         self.convs, self._conv_rung = convs, 0                       # (see BaselineAnimator / _render)
+        self.motion_regressor = motion_regressor                     # (see BaselineAnimator)
         self.encoder = encoder if encoder is not None else nets.EncoderWithZ()
         self.projector = decoder if decoder is not None else nets.DecoderPconv2(64, 3)
         self.net_bg = net_bg if net_bg is not None else nets.BGDecoder()
@@ -403,9 +429,11 @@ class SLRv1Animator(torch.nn.Module, _ConvRung):
         return clip
 
     @torch.no_grad()
-    def begin_clip(self, image, motion, N, shard=None, alpha_region=None, frames=None, convs=None):
-        """alpha_region [1,1,H,W]: optional edit mask (:867-906, 1079-1080): 1 = composite, 0 = fluid layer only."""
+    def begin_clip(self, image, motion, N, shard=None, alpha_region=None, frames=None, convs=None, motion_mask=None, motion_hint=None):
+        """alpha_region [1,1,H,W]: optional edit mask (:867-906, 1079-1080): 1 = composite, 0 = fluid layer only.  motion None:
+        predicted by the motion regressor (BaselineAnimator.begin_clip)."""
         policy = convs or self.convs
+        motion = self._motion(image, motion, motion_mask, motion_hint)
         plan = MotionPlan(motion, N, frames)
         fs, Z = _encode(self.encoder, image, shard, policy, self)
         bg = torch.tanh(_encode(self.net_bg, image, None, policy, self, "background network"))   # test_v1_4eval_rawsize.py:209, :925-927
@@ -468,13 +496,13 @@ class SLRv1Animator(torch.nn.Module, _ConvRung):
         assert fs.shape[0] == 1
         a = self.net_alpha_encoder(image)                           # :938
         bg = torch.tanh(batch["BGImg"][0])                          # :925-927
-        clip = self._clip(fs, Z.view(1, 1, fs.shape[2], fs.shape[3]), batch["motions"][0], end - start + 1, a, bg,
+        clip = self._clip(fs, Z.view(1, 1, fs.shape[2], fs.shape[3]), self._batch_motion(batch), end - start + 1, a, bg,
                           batch.get("alpha_region"), frames=[middle - start])
         return self._decode(clip, *clip.features(middle - start))
 
     @torch.no_grad()
     def synthesize(self, image, motion, N, frames=None, overlap=False, on_frame=None, shard=None, keys=None,
-                   alpha_region=None, batch=None, convs=None):
+                   alpha_region=None, batch=None, convs=None, motion_mask=None, motion_hint=None):
         """keys=None: PredImg frames [n,3,H,W] (as BaselineAnimator.synthesize).  keys=("PredImg", "FluidImg",
         "CompositeFluidAlpha", "BGImg", ...): a dict of those outputs of forward_flow, stacked over the frames
         ("BGImg" and "AlphaRegionMask" are frame-invariant: one [1,.,H,W] tensor) -- what
@@ -496,7 +524,7 @@ class SLRv1Animator(torch.nn.Module, _ConvRung):
                 raise KeyError(f"SLRv1Animator.synthesize: {k!r} needs an alpha_region")
         if on_frame is not None and "PredImg" not in want:
             raise KeyError("SLRv1Animator.synthesize: on_frame receives PredImg frames: request that key")
-        clip = self.begin_clip(image, motion, N, shard, alpha_region, frames, convs=policy)
+        clip = self.begin_clip(image, motion, N, shard, alpha_region, frames, convs=policy, motion_mask=motion_mask, motion_hint=motion_hint)
         H, W = image.shape[2:]
         outs = {k: image.new_empty(len(frames), channels[k], H, W) for k in want if k not in once}
         if "BGImg" in want:

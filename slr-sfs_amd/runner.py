@@ -11,40 +11,76 @@ import time
 
 import torch
 
-from . import io, nets, parallel, pipeline
+from . import io, motion as motion_mod, nets, parallel, pipeline
 
 V1_NETS = ("encoder", "projector", "net_bg", "net_alpha_encoder", "net_alpha_decoder")
 
 
-def load_model(ckpt, v1, dev):
+def load_model(ckpt, v1, dev, motion_ckpt=None):
     """BaselineAnimator / SLRv1Animator on ``dev``; ``ckpt``: a reference checkpoint (``state_dict`` with
     ``model.module.<net>.`` keys, ``opts`` = the training Namespace) or None / 'None' for random-init networks.
+    The animator gets a motion regressor (motion.MotionRegressor) when the checkpoint was trained with --train_motion (its
+    ``model.module.motion_regressor.motion_predictor.`` keys) or from ``motion_ckpt``, a motion checkpoint of train_motion_unet.py
+    (``model.module.motion_predictor.`` keys; it wins over the one of ``ckpt``).
     (Like the reference's scripts, this unpickles the file -- the Namespace is a pickled object: only load checkpoints you trust.)"""
     opts, sd = None, None
     if ckpt not in (None, "None", "none", ""):
         blob = torch.load(ckpt, map_location="cpu", weights_only=False)
         sd, opts = blob["state_dict"], blob.get("opts")
+    regressor = None
+    if motion_ckpt not in (None, "None", "none", ""):
+        mblob = torch.load(motion_ckpt, map_location="cpu", weights_only=False)
+        regressor = motion_mod.MotionRegressor(mblob.get("opts"), mblob["state_dict"])
+    elif sd is not None and pipeline._flag(opts, "train_motion"):
+        regressor = motion_mod.MotionRegressor(opts, sd, motion_mod.PREFIX_JOINT)
     if sd is None:
         torch.manual_seed(0)                       # random-init networks (plumbing / timing): the same on every rank
     model = pipeline.SLRv1Animator(opts=opts) if v1 else pipeline.BaselineAnimator(opts=opts)
     if sd is not None:
         for name in (V1_NETS if v1 else V1_NETS[:2]):
             nets.load_reference_state_dict(getattr(model, name), sd, "model.module." + name + ".")
+    model.motion_regressor = regressor
     return model.to(dev).eval()
 
 
+def predict_scene_motion(model, image, flow, W, points=None):
+    """The motion test script's prediction (test_motion_4eval_rawsize_threshold.py:155-219) on a [1,3,W,W] device image: mask (and
+    hints) from the scene's flow [1,2,h,w] (motion.motion_inputs_from_flow), then the regressor.  Returns (motion [1,2,W,W] on the
+    device, speed override): the hint branch animates at speed 1 whatever the command line says (:164), else None."""
+    reg = model.motion_regressor
+    if reg is None:
+        raise ValueError("predict_motion: the model has no motion regressor (a checkpoint trained with --train_motion, or --motion-ckpt)")
+    mask = hint = None
+    if reg.use_mask:
+        mask, hint = motion_mod.motion_inputs_from_flow(flow, W, points=points, hints=reg.use_hint)
+        mask = mask.to(image.device)
+        hint = None if hint is None else hint.to(image.device)
+    pred = reg.forward_flow(image, mask, hint)["PredMotion"]
+    return pred, (1.0 if reg.use_hint else None)
+
+
 def animate_scene(model, image_path, flow_path, out_dir, name, H, W, N, speed, align=None, rank=0, world=1, group=None,
-                  video=True, half_size=False):
+                  video=True, half_size=False, predict_motion=False, hint_points=None, write_motion=False):
     """One scene -> out_dir/name/PredImg/%06d.png (2-layer model: + FluidImg/, CompositeFluidAlpha/, BGImg.png;
     test_v1_4eval_rawsize.py:240-284), written by rank 0, at the raw size of the image (the *_rawsize scripts) or at half
-    of it (half_size: test_baseline_4eval.py / test_v1_4eval.py:160-161).  Returns (seconds of device work, frame dir)."""
+    of it (half_size: test_baseline_4eval.py / test_v1_4eval.py:160-161).  predict_motion: the motion is predicted from the image by
+    the model's motion regressor, with the mask / hints derived from the scene's flow (predict_scene_motion; ``hint_points`` [(y, x)]
+    pins the hints; the hint branch forces speed 1), every rank predicting it; write_motion: rank 0 also writes the field used as
+    out_dir/name/Motion.flo.  Returns (seconds of device work, frame dir)."""
     v1 = isinstance(model, pipeline.SLRv1Animator)
     dev = next(model.parameters()).device
     image, (raw_w, raw_h) = io.load_image(image_path, H, W)
-    motion = pipeline.prepare_motion(io.load_motion(flow_path), H, W, speed, io.speed_align(align, name), N)
+    image = image.to(dev)
+    if predict_motion:
+        if H != W:
+            raise ValueError("predict_motion: the motion test script works on a square W x W grid")
+        pred, forced = predict_scene_motion(model, image, io.load_motion(flow_path), W, hint_points)
+        motion = pipeline.prepare_motion(pred, H, W, speed if forced is None else forced, io.speed_align(align, name), N)
+    else:
+        motion = pipeline.prepare_motion(io.load_motion(flow_path), H, W, speed, io.speed_align(align, name), N)
     if half_size:
         raw_w, raw_h = raw_w // 2, raw_h // 2
-    image, motion = image.to(dev), motion.to(dev)
+    motion = motion.to(dev)
     mine = parallel.shard_frames(N, rank, world)      # (N < world: some ranks render nothing -- they still enter every
     shard = (rank, world, group) if world > 1 else None   # collective below, with empty [0,.,H,W] contributions)
     torch.cuda.synchronize(dev)
@@ -61,6 +97,9 @@ def animate_scene(model, image_path, flow_path, out_dir, name, H, W, N, speed, a
     scene = os.path.join(out_dir, name)
     frame_dir = os.path.join(scene, "PredImg")
     if rank == 0:
+        if write_motion:
+            os.makedirs(scene, exist_ok=True)
+            io.write_flo(os.path.join(scene, "Motion.flo"), motion[0].permute(1, 2, 0).cpu().numpy())
         io.save_frames(io.frames_to_uint8(clips["PredImg"], (raw_h, raw_w)), scene)
         if v1:
             io.save_frames(io.frames_to_uint8(clips["FluidImg"], (raw_h, raw_w)), scene, key="FluidImg")

@@ -4,7 +4,9 @@
 (test_animating/CLAW/test_all_CLAW_scenes.py:86-96) with the same positional arguments; writes
 OUTDIR/NAME/PredImg/%06d.png (--v1: also FluidImg/, CompositeFluidAlpha/, BGImg.png).  Without a checkpoint (CKPT = None)
 the networks are random-initialised (plumbing / timing only).  --v1 runs the 2-layer SLR model (test_v1_4eval_rawsize.py).
-Under torchrun the frames of the clip are rendered by all ranks (slr_sfs_amd/runner.py)."""
+Under torchrun the frames of the clip are rendered by all ranks (slr_sfs_amd/runner.py).
+--motion-ckpt MOTION.pth (or a CKPT trained with --train_motion plus --predict-motion): the motion is predicted from the image by the
+motion U-Net (test_animating/test_motion_4eval_rawsize_threshold.py), FLOW only supplies its moving-region mask and hints."""
 import argparse
 import os
 import sys
@@ -39,11 +41,23 @@ def main():
     ap.add_argument("--H", type=int, default=None, help="working height (default: W, square like the reference)")
     ap.add_argument("--v1", action="store_true")
     ap.add_argument("--half-size", action="store_true", help="write frames at half the raw size (test_baseline_4eval.py / test_v1_4eval.py)")
+    ap.add_argument("--motion-ckpt", default=None,
+                    help="motion checkpoint (train_motion_unet.py): predict the motion from the image; FLOW then only gives the moving-region "
+                         "mask and the motion hints.  With a mask + hint network the clip is animated at speed 1 whatever SPEED says "
+                         "(the reference's motion test script forces it)")
+    ap.add_argument("--predict-motion", action="store_true",
+                    help="predict the motion with the motion regressor of CKPT (trained with --train_motion); implied by --motion-ckpt")
+    ap.add_argument("--hint-points", default=None,
+                    help="the 5 hint pixels 'y,x;y,x;...' at the flow's resolution (default: a deterministic k-means of the moving region, "
+                         "whose positions are not those of the reference's sklearn KMeans)")
+    ap.add_argument("--write-motion", action="store_true", help="also write the motion field used as OUTDIR/NAME/Motion.flo")
     a = ap.parse_args()
     rank, world, dev = init_ranks()
-    model = runner.load_model(a.ckpt, a.v1, dev)
+    model = runner.load_model(a.ckpt, a.v1, dev, motion_ckpt=a.motion_ckpt)
+    points = None if a.hint_points is None else [tuple(int(v) for v in p.split(",")) for p in a.hint_points.split(";")]
     dt, out = runner.animate_scene(model, a.image, a.flow, a.outdir, a.name, a.H or a.W, a.W, a.N, a.speed, a.align, rank, world,
-                                   half_size=a.half_size)
+                                   half_size=a.half_size, predict_motion=bool(a.motion_ckpt or a.predict_motion), hint_points=points,
+                                   write_motion=a.write_motion)
     if rank == 0:
         print(f"{a.N} frames at {a.H or a.W}x{a.W} on {world} GPU(s) in {dt:.2f} s ({a.N / dt:.1f} frames/s) -> {out}")
     if world > 1:
