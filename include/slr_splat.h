@@ -402,7 +402,7 @@ int slr_pconv3x3_forward(const float *x, const float *pre_scale, const float *pr
  * the skip convolution over skip_cin more input channels (one tap): no separate 1x1 kernel, no write and re-read of its result.
  * Against the two-kernel form (slr_conv1x1_forward -> residual) the result differs by the order of the last additions only (fp32
  * rounding; tests/test_gpu_parity.py).  skip_wsplit: slr_conv1x1_split_weights(Cout, skip_cin, skip_wscale); the skip input shares
- * `xscale`.  Split-f16 rung only (no SLR_CONV_F32 / _WINO), main input and skip input channel-blocked (SLR_CONV_IN_B8 and
+ * `xscale`.  No SLR_CONV_WINO; with SLR_CONV_F32 only Cout > 64 and skip_wscale = 1; main input and skip input channel-blocked (SLR_CONV_IN_B8 and
  * SLR_CONV_SKIP_B8 both set, skip_cin % 8 == 0), Cout > 4; anything else is SLR_E_BADARG -- callers keep the two-kernel form there
  * (the networks' 3-channel first blocks and 65- / 3-channel ends).
  * With SLR_CONV_POOL_OUT (and SLR_CONV_OUT_B8, Cout > 64) the "Down" block's nn.AvgPool2d(3, stride=2, padding=1) (blocks.py:196-199)

@@ -1191,85 +1191,63 @@ SLR_EXPORT int slr_conv_saturation_record(unsigned *host_slot, void *stream) {
     return 0;
 }
 
-// Cout <= 4: the weight buffer holds plain fp32 weights [ci padded to 8][tap][4] on either rung (conv_few.hpp); it fits the split layout's bytes
-static int conv_few_weights(const float *w, void *wbuf, int Cout, int Cin, hipStream_t st) {
-    const int CinP = conv_few_cin_pad(Cin);
-    static_assert(36 * sizeof(float) * 8 <= 32 * 16 * 9 * 2 * sizeof(_Float16), "8 input channels of plain weights fit 16 of the split layout");
-    hipLaunchKernelGGL(conv_few_weights_kernel, dim3((CinP * 36 + 255) / 256), dim3(256), 0, st, w, (float *)wbuf, Cout, Cin, CinP);
-    SLR_CHECK_LAUNCH();
-    return 0;
+// ---- host side of the 3x3 / 1x1 convolutions ------------------------------------------------------------------------------------------
+
+// Run-time flags -> template arguments: fn(std::bool_constant<b>...) with the values of the flags, in order ...
+template <class F> static int dispatch(F &&fn) { return fn(); }
+template <class F, class... B> static int dispatch(F &&fn, bool b, B... flags) {
+    if (b) return dispatch([&](auto... c) { return fn(std::true_type{}, c...); }, flags...);
+    return dispatch([&](auto... c) { return fn(std::false_type{}, c...); }, flags...);
+}
+// ... and an int: fn(std::integral_constant<int, V>) for the first V of the list equal to v (the last one for any other value)
+template <int V, int... Vs, class F> static int dispatch_int(int v, F &&fn) {
+    if constexpr (sizeof...(Vs) == 0) return fn(std::integral_constant<int, V>{});
+    else return v == V ? fn(std::integral_constant<int, V>{}) : dispatch_int<Vs...>(v, fn);
+}
+// (the checks in front of every launch keep the requests within the instantiations that are built)
+static int conv_not_built() {
+    set_error("conv: no kernel instantiation for these layout flags");
+    return SLR_E_BADARG;
 }
 
-template <int NCO>
-static int conv_few_launch(ConvArgs &a, bool in_b8, hipStream_t st) {
-    const dim3 grid(((a.W + CF_BW - 1) / CF_BW) * ((a.H + CF_BH - 1) / CF_BH), 1, a.N);
-    if (a.skip_out) {                                   // (the *_skipout entry points: channel-blocked input)
-        if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_few_kernel<NCO, true, true, true>), grid, dim3(CF_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_few_kernel<NCO, false, true, true>), grid, dim3(CF_THREADS), 0, st, a);
-        SLR_CHECK_LAUNCH();
-        return 0;
-    }
-    if (a.pre != PRE_NONE && in_b8) hipLaunchKernelGGL((conv3x3_few_kernel<NCO, true, true>), grid, dim3(CF_THREADS), 0, st, a);
-    else if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_few_kernel<NCO, true, false>), grid, dim3(CF_THREADS), 0, st, a);
-    else if (in_b8) hipLaunchKernelGGL((conv3x3_few_kernel<NCO, false, true>), grid, dim3(CF_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_few_kernel<NCO, false, false>), grid, dim3(CF_THREADS), 0, st, a);
-    SLR_CHECK_LAUNCH();
-    return 0;
-}
-
-SLR_EXPORT size_t slr_conv3x3_weight_bytes(int Cout, int Cin) {
-    if (Cout <= 0 || Cin <= 0) return 0;
-    return (size_t)conv_cout_pad(Cout) * conv_cin_pad(Cin) * 9 * 2 * sizeof(_Float16);
-}
-
-SLR_EXPORT int slr_conv3x3_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
-    SLR_CHECK_ARG(w && wsplit, "null pointer");
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)conv_cout_pad(Cout) * conv_cin_pad(Cin) * 9 < (1LL << 30), "sizes");
-    SLR_CHECK_ARG(wscale > 0.0f, "wscale");
-    if (Cout <= CF_MAXCO) return conv_few_weights(w, wsplit, Cout, Cin, (hipStream_t)stream);      // (plain fp32 weights: conv_few.hpp)
-    const int CoutP = conv_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    const int total = CoutP * CinP * 9;
-    hipLaunchKernelGGL(conv_split_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                       (_Float16 *)wsplit, Cout, Cin, CoutP, CinP, 9, wscale);
-    SLR_CHECK_LAUNCH();
+static int check_xscale(float xscale) {
+    int ex = 0;
+    SLR_CHECK_ARG(xscale > 0.0f && xscale <= CV_XSCALE && frexpf(xscale, &ex) == 0.5f, "xscale: a power of two in (0, 64]");
     return 0;
 }
 
 static int conv_check_layout(int layout, const void *in, const void *out, int Cin, int Cout, const void *residual,
-                             bool derived_mask);
+                             bool derived_mask) {
+    layout &= ~(SLR_CONV_F32 | SLR_CONV_WINO | SLR_CONV_SKIP_B8 | SLR_CONV_POOL_OUT | SLR_CONV_UP_OUT);      // (the last three: conv_set_skip)
+    SLR_CHECK_ARG((layout & ~(SLR_CONV_IN_B8 | SLR_CONV_OUT_B8 | SLR_CONV_RES_B8)) == 0, "layout flags");
+    SLR_CHECK_ARG(!(layout & SLR_CONV_RES_B8) || ((layout & SLR_CONV_OUT_B8) && residual && !((uintptr_t)residual & 15)),
+                  "a channel-blocked residual goes with a channel-blocked output");
+    SLR_CHECK_ARG(!(layout & SLR_CONV_IN_B8) || (Cin % 8 == 0 && !((uintptr_t)in & 15) && !derived_mask),
+                  "channel-blocked input needs Cin % 8 == 0, a 16-byte aligned tensor and an explicit mask");
+    SLR_CHECK_ARG(!(layout & SLR_CONV_OUT_B8) || (Cout % 8 == 0 && !((uintptr_t)out & 15)),
+                  "channel-blocked output needs Cout % 8 == 0 and a 16-byte aligned tensor");
+    return 0;
+}
+
+static int conv_check_dims(int N, int Cin, int Cout, int H, int W) {
+    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && Cout > 0 && Cout < (1 << 20) && H > 0 && W > 0 &&
+                  (long long)Cin * H * W < (1LL << 31) && (long long)N * Cout * H * W < (1LL << 40), "sizes");
+    return 0;
+}
 
 // 1x1: output channels in groups of NCT*32 <= 128 per workgroup row (64 accumulator registers: 3 waves per SIMD;
 // wider layers re-read the input once per 128 channels, mostly from L2; 64-channel rows measured the same)
 static int conv1x1_nct(int Cout) { const int t = (Cout + 31) / 32; return t > 2 ? 4 : (t > 1 ? 2 : 1); }
 static int conv1x1_cout_pad(int Cout) { const int g = conv1x1_nct(Cout) * 32; return (Cout + g - 1) / g * g; }
 
+SLR_EXPORT size_t slr_conv3x3_weight_bytes(int Cout, int Cin) {
+    if (Cout <= 0 || Cin <= 0) return 0;
+    return (size_t)conv_cout_pad(Cout) * conv_cin_pad(Cin) * 9 * 2 * sizeof(_Float16);
+}
+
 SLR_EXPORT size_t slr_conv1x1_weight_bytes(int Cout, int Cin) {
     if (Cout <= 0 || Cin <= 0) return 0;
     return (size_t)conv1x1_cout_pad(Cout) * conv_cin_pad(Cin) * 2 * sizeof(_Float16);
-}
-
-SLR_EXPORT int slr_conv1x1_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
-    SLR_CHECK_ARG(w && wsplit, "null pointer");
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)conv1x1_cout_pad(Cout) * conv_cin_pad(Cin) < (1LL << 30), "sizes");
-    SLR_CHECK_ARG(wscale > 0.0f, "wscale");
-    const int CoutP = conv1x1_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    const int total = CoutP * CinP;
-    hipLaunchKernelGGL(conv_split_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                       (_Float16 *)wsplit, Cout, Cin, CoutP, CinP, 1, wscale);
-    SLR_CHECK_LAUNCH();
-    return 0;
-}
-
-SLR_EXPORT int slr_conv3x3_f32_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    SLR_CHECK_ARG(w && wfrag, "null pointer");
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)conv_cout_pad(Cout) * conv_cin_pad(Cin) * 9 < (1LL << 30), "sizes");
-    if (Cout <= CF_MAXCO) return conv_few_weights(w, wfrag, Cout, Cin, (hipStream_t)stream);
-    const int CoutP = conv_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    const int total = CoutP * CinP * 9;
-    hipLaunchKernelGGL(conv_f32_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (float *)wfrag,
-                       Cout, Cin, CoutP, CinP, 9, 0);
-    SLR_CHECK_LAUNCH();
-    return 0;
 }
 
 SLR_EXPORT size_t slr_conv3x3_wino_weight_bytes(int Cout, int Cin) {
@@ -1277,31 +1255,52 @@ SLR_EXPORT size_t slr_conv3x3_wino_weight_bytes(int Cout, int Cin) {
     return (size_t)wino_cout_pad(Cout) * conv_cin_pad(Cin) * 16 * sizeof(float);
 }
 
-SLR_EXPORT int slr_conv3x3_wino_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    SLR_CHECK_ARG(w && wfrag, "null pointer");
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)wino_cout_pad(Cout) * conv_cin_pad(Cin) * 16 < (1LL << 30), "sizes");
-    const int CoutP = wino_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    hipLaunchKernelGGL(conv_wino_weights_kernel, dim3((CoutP * CinP + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (float *)wfrag,
-                       Cout, Cin, CoutP, CinP);
+// The weight buffer of every forward entry point, in fragment order: WSPLIT hi / lo f16 halves scaled by wscale, WF32 fp32 values,
+// WWINO fp32 values in the Winograd domain (3x3 only); taps 9 (3x3) or 1 (1x1).  Cout <= 4 3x3 layers hold plain fp32 weights
+// [ci padded to 8][tap][4] on either rung (conv_few.hpp); they fit the split layout's bytes.
+enum WeightForm { WSPLIT, WF32, WWINO };
+static int conv_weights(WeightForm form, int taps, const float *w, void *buf, int Cout, int Cin, float wscale, void *stream) {
+    static_assert(36 * sizeof(float) * 8 <= 32 * 16 * 9 * 2 * sizeof(_Float16), "8 input channels of plain weights fit 16 of the split layout");
+    SLR_CHECK_ARG(w && buf, "null pointer");
+    const int CoutP = form == WWINO ? wino_cout_pad(Cout) : taps == 9 ? conv_cout_pad(Cout) : conv1x1_cout_pad(Cout), CinP = conv_cin_pad(Cin);
+    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)CoutP * CinP * (form == WWINO ? 16 : taps) < (1LL << 30), "sizes");
+    SLR_CHECK_ARG(form != WSPLIT || wscale > 0.0f, "wscale");
+    hipStream_t st = (hipStream_t)stream;
+    const int total = form == WWINO ? CoutP * CinP : CoutP * CinP * taps;
+    if (form != WWINO && taps == 9 && Cout <= CF_MAXCO) {
+        const int CinF = conv_few_cin_pad(Cin);
+        hipLaunchKernelGGL(conv_few_weights_kernel, dim3((CinF * 36 + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CinF);
+    } else if (form == WSPLIT) {
+        hipLaunchKernelGGL(conv_split_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (_Float16 *)buf, Cout, Cin, CoutP, CinP,
+                           taps, wscale);
+    } else if (form == WF32) {
+        hipLaunchKernelGGL(conv_f32_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CoutP, CinP,
+                           taps, taps == 1 ? 1 : 0);
+    } else {
+        hipLaunchKernelGGL(conv_wino_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CoutP, CinP);
+    }
     SLR_CHECK_LAUNCH();
     return 0;
+}
+
+SLR_EXPORT int slr_conv3x3_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
+    return conv_weights(WSPLIT, 9, w, wsplit, Cout, Cin, wscale, stream);
+}
+
+SLR_EXPORT int slr_conv1x1_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
+    return conv_weights(WSPLIT, 1, w, wsplit, Cout, Cin, wscale, stream);
+}
+
+SLR_EXPORT int slr_conv3x3_f32_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
+    return conv_weights(WF32, 9, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_f32_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    SLR_CHECK_ARG(w && wfrag, "null pointer");
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)conv1x1_cout_pad(Cout) * conv_cin_pad(Cin) < (1LL << 30), "sizes");
-    const int CoutP = conv1x1_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    const int total = CoutP * CinP;
-    hipLaunchKernelGGL(conv_f32_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (float *)wfrag,
-                       Cout, Cin, CoutP, CinP, 1, 1);
-    SLR_CHECK_LAUNCH();
-    return 0;
+    return conv_weights(WF32, 1, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
-static int check_xscale(float xscale) {
-    int ex = 0;
-    SLR_CHECK_ARG(xscale > 0.0f && xscale <= CV_XSCALE && frexpf(xscale, &ex) == 0.5f, "xscale: a power of two in (0, 64]");
-    return 0;
+SLR_EXPORT int slr_conv3x3_wino_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
+    return conv_weights(WWINO, 9, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_forward(const float *in, const void *wsplit, const float *bias, float *out, int N, int Cin,
@@ -1322,150 +1321,14 @@ SLR_EXPORT int slr_conv1x1_forward(const float *in, const void *wsplit, const fl
     const int ob8 = (layout & SLR_CONV_OUT_B8) ? 1 : 0;
     unsigned *satp = nullptr;
     if (int e = sat_counter(&satp)) return e;
-#define C1_LAUNCH(T)                                                                                                       \
-    do {                                                                                                                   \
-        if (f32 && (layout & SLR_CONV_IN_B8)) hipLaunchKernelGGL((conv1x1_split_kernel<T, true, true>), grid, dim3(256), 0, st, in, (const h8 *)wsplit, bias, out, Cin, Cout, HW, nchunk, unscale, xscale, ob8, satp); \
-        else if (f32) hipLaunchKernelGGL((conv1x1_split_kernel<T, false, true>), grid, dim3(256), 0, st, in, (const h8 *)wsplit, bias, out, Cin, Cout, HW, nchunk, unscale, xscale, ob8, satp); \
-        else if (layout & SLR_CONV_IN_B8) hipLaunchKernelGGL((conv1x1_split_kernel<T, true>), grid, dim3(256), 0, st, in, (const h8 *)wsplit, bias, out, Cin, Cout, HW, nchunk, unscale, xscale, ob8, satp); \
-        else hipLaunchKernelGGL((conv1x1_split_kernel<T, false>), grid, dim3(256), 0, st, in, (const h8 *)wsplit, bias, out, Cin, Cout, HW, nchunk, unscale, xscale, ob8, satp); \
-    } while (0)
-    if (nct == 4) C1_LAUNCH(4); else if (nct == 2) C1_LAUNCH(2); else C1_LAUNCH(1);
-#undef C1_LAUNCH
-    SLR_CHECK_LAUNCH();
-    return 0;
-}
-
-template <bool F32>
-static int conv_launch_t(ConvArgs &a, bool in_b8, hipStream_t st);
-
-static int conv_wino_launch(ConvArgs &a, bool in_b8, hipStream_t st) {
-    static LdsOptIn attr[4];
-    const int which = (a.pre != PRE_NONE ? 2 : 0) + (in_b8 ? 1 : 0);
-    const void *fn = which == 3 ? (const void *)conv3x3_wino_kernel<true, true> : which == 2 ? (const void *)conv3x3_wino_kernel<true, false>
-                   : which == 1 ? (const void *)conv3x3_wino_kernel<false, true> : (const void *)conv3x3_wino_kernel<false, false>;
-    if (int e = lds_opt_in(fn, (int)WN_LDS_BYTES, attr[which])) return e;
-    a.tiles_x = (a.W + WN_BW - 1) / WN_BW;
-    a.nchunk = conv_cin_pad(a.Cin) / 16;
-    a.xscale = 1.0f; a.unscale = 1.0f;
-    const int blocks = a.tiles_x * ((a.H + WN_BH - 1) / WN_BH), ngrp = wino_cout_pad(a.Cout) / 64;
-    const dim3 grid((blocks + WN_SLICE - 1) / WN_SLICE * WN_SLICE * ngrp, 1, a.N);
-    a.wino_groups = ngrp;
-#ifdef SLR_TRACE
-    a.trace = g_trace;
-#endif
-    if (which == 3) hipLaunchKernelGGL((conv3x3_wino_kernel<true, true>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
-    else if (which == 2) hipLaunchKernelGGL((conv3x3_wino_kernel<true, false>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
-    else if (which == 1) hipLaunchKernelGGL((conv3x3_wino_kernel<false, true>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino_kernel<false, false>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
-    SLR_CHECK_LAUNCH();
-    return 0;
-}
-
-static int conv_launch(ConvArgs &a, float wscale, float xscale, bool in_b8, bool f32, hipStream_t st, bool wino = false) {
-    if (int e = check_xscale(xscale)) return e;
-    SLR_CHECK_ARG(!f32 || (wscale == 1.0f && xscale == 1.0f), "the fp32 rung takes no operand scales (wscale = xscale = 1)");
-    SLR_CHECK_ARG(!wino || (f32 && a.Cout > CF_MAXCO), "SLR_CONV_WINO goes with SLR_CONV_F32 and more than 4 output channels");
-    SLR_CHECK_ARG(!wino || a.pre == PRE_NONE || a.Cin <= WN_MAXCIN, "SLR_CONV_WINO with a prologue supports Cin <= 256");
-    if (wino) return conv_wino_launch(a, in_b8, st);
-    if (a.Cout <= CF_MAXCO) {                           // fp32 FMAs on the vector ALUs on either rung: no operand scales, nothing saturates
-        switch (a.Cout) {
-            case 1: return conv_few_launch<1>(a, in_b8, st);
-            case 2: return conv_few_launch<2>(a, in_b8, st);
-            case 3: return conv_few_launch<3>(a, in_b8, st);
-            default: return conv_few_launch<4>(a, in_b8, st);
-        }
-    }
-    a.tiles_x = (a.W + CV_W - 1) / CV_W;
-    a.nchunk = conv_cin_pad(a.Cin) / 16;
-    a.xscale = xscale;
-    a.unscale = 1.0f / (xscale * wscale);
-    if (int e = sat_counter(&a.sat)) return e;
-    return f32 ? conv_launch_t<true>(a, in_b8, st) : conv_launch_t<false>(a, in_b8, st);
-}
-
-template <bool F32>
-static int conv_launch_t(ConvArgs &a, bool in_b8, hipStream_t st) {
-    const int tiles = a.tiles_x * ((a.H + CV_H - 1) / CV_H);
-    int ct = conv_cout_tile(a.Cout);
-    // NCHW input WITH a prologue and > 64 output channels: 24 scalar staging loads + the prologue table + 128
-    // accumulator registers do not fit 256 VGPRs (the <1,4,true,false> instantiation spilled 14-27 of them); that
-    // combination runs as two 64-channel workgroup rows instead (no network on the path uses it: wide layers read
-    // channel-blocked activations).  The weight buffer is indexed by 32-channel tiles, so any row width reads it.
-    if (ct == 128 && a.pre != PRE_NONE && !in_b8) ct = 64;
-    const dim3 grid(tiles, conv_cout_pad(a.Cout) / ct, a.N);
-    {
-        if (a.skip_in) {                    // (conv_set_skip: channel-blocked main input, more than 4 output channels; fp32 rung: more than 64)
-#define CV_SKIP(WCO)                                                                                            \
-    do {                                                                                                       \
-        if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_split_kernel<1, WCO, true, true, F32, true>), grid, dim3(CV_THREADS), 0, st, a);   \
-        else hipLaunchKernelGGL((conv3x3_split_kernel<1, WCO, false, true, F32, true>), grid, dim3(CV_THREADS), 0, st, a);                   \
-    } while (0)
-            if (a.resample) {               // (conv_set_skip: 128-channel workgroup rows)
-                if (a.resample == 2) {
-                    if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, true, true, F32, true, false, true>), grid, dim3(CV_THREADS), 0, st, a);
-                    else hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, true, F32, true, false, true>), grid, dim3(CV_THREADS), 0, st, a);
-                    SLR_CHECK_LAUNCH();
-                    const int items = 2 * a.tiles_y * 2 * a.W + 2 * a.tiles_x * 2 * a.H;
-                    hipLaunchKernelGGL(upsample_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
-                                       (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
-                    SLR_CHECK_LAUNCH();
-                    return 0;
-                }
-                if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, true, true, F32, true, true>), grid, dim3(CV_THREADS), 0, st, a);
-                else hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, true, F32, true, true>), grid, dim3(CV_THREADS), 0, st, a);
-                SLR_CHECK_LAUNCH();
-                const int OH = (a.H - 1) / 2 + 1, OW = (a.W - 1) / 2 + 1;
-                const int items = (a.tiles_y - 1) * OW + (a.tiles_x - 1) * OH;
-                if (items > 0) {
-                    hipLaunchKernelGGL(pool_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
-                                       (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
-                    SLR_CHECK_LAUNCH();
-                }
-                return 0;
-            }
-            if (ct == 128) CV_SKIP(4);
-            else if constexpr (!F32) { if (ct == 64) CV_SKIP(2); else CV_SKIP(1); }
-#undef CV_SKIP
-            SLR_CHECK_LAUNCH();
+    dispatch_int<4, 2, 1>(nct, [&](auto nct_) {
+        return dispatch([&](auto b8, auto f32_) {
+            hipLaunchKernelGGL((conv1x1_split_kernel<nct_, b8, f32_>), grid, dim3(256), 0, st, in, (const h8 *)wsplit, bias, out, Cin, Cout,
+                               HW, nchunk, unscale, xscale, ob8, satp);
             return 0;
-        }
-    }
-#define CV_LAUNCH(CPW, WCO)                                                                                     \
-    do {                                                                                                       \
-        if (a.pre != PRE_NONE && in_b8) hipLaunchKernelGGL((conv3x3_split_kernel<CPW, WCO, true, true, F32>), grid, dim3(CV_THREADS), 0, st, a);    \
-        else if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_split_kernel<CPW, WCO, true, false, F32>), grid, dim3(CV_THREADS), 0, st, a);      \
-        else if (in_b8) hipLaunchKernelGGL((conv3x3_split_kernel<CPW, WCO, false, true, F32>), grid, dim3(CV_THREADS), 0, st, a);                  \
-        else hipLaunchKernelGGL((conv3x3_split_kernel<CPW, WCO, false, false, F32>), grid, dim3(CV_THREADS), 0, st, a);                            \
-    } while (0)
-    if (ct == 128) {                        // one 32-channel tile x all 8 rows per wave: a quarter of the weight-fragment
-                                            // traffic of 4 x 2 tiles per wave would need, half of <2,2> (+3..5 % measured)
-        if (a.pre != PRE_NONE) hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, true, true, F32>), grid, dim3(CV_THREADS), 0, st, a);   // (in_b8)
-        else if (in_b8) hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, true, F32>), grid, dim3(CV_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, false, F32>), grid, dim3(CV_THREADS), 0, st, a);
-    }
-    else if (ct == 64) CV_LAUNCH(1, 2);     // 1 tile x 4 rows per wave: half the weight-fragment loads of <2,1> (+4 %)
-    else CV_LAUNCH(1, 1);
-#undef CV_LAUNCH
+        }, (layout & SLR_CONV_IN_B8) != 0, f32);
+    });
     SLR_CHECK_LAUNCH();
-    return 0;
-}
-
-static int conv_check_layout(int layout, const void *in, const void *out, int Cin, int Cout, const void *residual,
-                             bool derived_mask) {
-    layout &= ~(SLR_CONV_F32 | SLR_CONV_WINO | SLR_CONV_SKIP_B8 | SLR_CONV_POOL_OUT | SLR_CONV_UP_OUT);      // (the last three: conv_set_skip)
-    SLR_CHECK_ARG((layout & ~(SLR_CONV_IN_B8 | SLR_CONV_OUT_B8 | SLR_CONV_RES_B8)) == 0, "layout flags");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_RES_B8) || ((layout & SLR_CONV_OUT_B8) && residual && !((uintptr_t)residual & 15)),
-                  "a channel-blocked residual goes with a channel-blocked output");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_IN_B8) || (Cin % 8 == 0 && !((uintptr_t)in & 15) && !derived_mask),
-                  "channel-blocked input needs Cin % 8 == 0, a 16-byte aligned tensor and an explicit mask");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_OUT_B8) || (Cout % 8 == 0 && !((uintptr_t)out & 15)),
-                  "channel-blocked output needs Cout % 8 == 0 and a 16-byte aligned tensor");
-    return 0;
-}
-
-static int conv_check_dims(int N, int Cin, int Cout, int H, int W) {
-    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && Cout > 0 && Cout < (1 << 20) && H > 0 && W > 0 &&
-                  (long long)Cin * H * W < (1LL << 31) && (long long)N * Cout * H * W < (1LL << 40), "sizes");
     return 0;
 }
 
@@ -1527,30 +1390,128 @@ static int conv_set_skip(ConvArgs &a, const SkipOp *sk, float xscale, int &layou
     return 0;
 }
 
-static int conv3x3_forward_impl(const float *in, const void *wsplit, const float *bias, const float *residual,
-                                   float *out, int N, int Cin, int Cout, int H, int W, float wscale, float xscale,
-                                   const float *pre_scale, const float *pre_shift, const SkipOp *sk, int layout, void *stream) {
-    SLR_CHECK_ARG(in && wsplit && out, "null pointer");
-    if (int e = conv_check_layout(layout, in, out, Cin, Cout, residual, false)) return e;
+// The conv3x3_split_kernel instantiations that are built.  Never: NCHW input with a prologue at 128-channel rows (24 scalar staging
+// loads + the prologue table + 128 accumulator registers do not fit 256 VGPRs: the <1,4,true,false> instantiation spilled 14-27 of them;
+// conv_launch runs that case as two 64-channel rows), SKIP with an NCHW input, POOL / UPS other than with SKIP at 128-channel rows,
+// SKIP on the fp32 rung other than at 128-channel rows (conv_set_skip refuses the requests that would need them).
+template <int WCO, bool PRE, bool B8, bool F32, bool SKIP, bool POOL, bool UPS>
+static constexpr bool conv_split_built() {
+    return !(WCO == 4 && PRE && !B8) && (B8 || !SKIP) && (!(POOL || UPS) || (SKIP && WCO == 4 && !(POOL && UPS))) &&
+           !(F32 && SKIP && WCO != 4);
+}
+
+static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipStream_t st) {
+    const bool in_b8 = (layout & SLR_CONV_IN_B8) != 0, f32 = (layout & SLR_CONV_F32) != 0, wino = (layout & SLR_CONV_WINO) != 0;
+    const bool pre = a.pre != PRE_NONE;
+    if (int e = check_xscale(xscale)) return e;
+    SLR_CHECK_ARG(!f32 || (wscale == 1.0f && xscale == 1.0f), "the fp32 rung takes no operand scales (wscale = xscale = 1)");
+    SLR_CHECK_ARG(!wino || (f32 && a.Cout > CF_MAXCO), "SLR_CONV_WINO goes with SLR_CONV_F32 and more than 4 output channels");
+    SLR_CHECK_ARG(!wino || !pre || a.Cin <= WN_MAXCIN, "SLR_CONV_WINO with a prologue supports Cin <= 256");
+    if (wino) {
+        a.tiles_x = (a.W + WN_BW - 1) / WN_BW;
+        a.nchunk = conv_cin_pad(a.Cin) / 16;
+        a.xscale = 1.0f; a.unscale = 1.0f;
+        const int blocks = a.tiles_x * ((a.H + WN_BH - 1) / WN_BH), ngrp = wino_cout_pad(a.Cout) / 64;
+        const dim3 grid((blocks + WN_SLICE - 1) / WN_SLICE * WN_SLICE * ngrp, 1, a.N);
+        a.wino_groups = ngrp;
+#ifdef SLR_TRACE
+        a.trace = g_trace;
+#endif
+        if (int e = dispatch([&](auto pre_, auto b8) {
+                static LdsOptIn attr;                   // (one per instantiation)
+                if (int e = lds_opt_in((const void *)conv3x3_wino_kernel<pre_, b8>, (int)WN_LDS_BYTES, attr)) return e;
+                hipLaunchKernelGGL((conv3x3_wino_kernel<pre_, b8>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
+                return 0;
+            }, pre, in_b8)) return e;
+        SLR_CHECK_LAUNCH();
+        return 0;
+    }
+    if (a.Cout <= CF_MAXCO) {                           // fp32 FMAs on the vector ALUs on either rung: no operand scales, nothing saturates
+        const dim3 grid(((a.W + CF_BW - 1) / CF_BW) * ((a.H + CF_BH - 1) / CF_BH), 1, a.N);
+        if (int e = dispatch_int<1, 2, 3, 4>(a.Cout, [&](auto nco) {
+                return dispatch([&](auto pre_, auto b8, auto skp) {
+                    if constexpr (b8 || !skp) hipLaunchKernelGGL((conv3x3_few_kernel<nco, pre_, b8, skp>), grid, dim3(CF_THREADS), 0, st, a);
+                    else return conv_not_built();        // (the *_skipout entry points: channel-blocked input)
+                    return 0;
+                }, pre, in_b8, a.skip_out != nullptr);
+            })) return e;
+        SLR_CHECK_LAUNCH();
+        return 0;
+    }
+    a.tiles_x = (a.W + CV_W - 1) / CV_W;
+    a.nchunk = conv_cin_pad(a.Cin) / 16;
+    a.xscale = xscale;
+    a.unscale = 1.0f / (xscale * wscale);
+    if (int e = sat_counter(&a.sat)) return e;
+    // 128-channel rows: one 32-channel tile x all 8 rows per wave, a quarter of the weight-fragment traffic of 4 x 2 tiles per wave,
+    // half of <2,2> (+3..5 % measured); 64: 1 tile x 4 rows per wave, half the weight-fragment loads of <2,1> (+4 %).  NCHW input with a
+    // prologue: 64-channel rows at most (see conv_split_built; no network on the path uses it: wide layers read channel-blocked
+    // activations).  The weight buffer is indexed by 32-channel tiles, so any row width reads it.
+    int ct = conv_cout_tile(a.Cout);
+    if (ct == 128 && pre && !in_b8) ct = 64;
+    const dim3 grid(a.tiles_x * ((a.H + CV_H - 1) / CV_H), conv_cout_pad(a.Cout) / ct, a.N);
+    if (int e = dispatch_int<4, 2, 1>(ct / 32, [&](auto wco) {
+            return dispatch([&](auto pre_, auto b8, auto f32_, auto skip, auto pool, auto ups) {
+                if constexpr (conv_split_built<wco, pre_, b8, f32_, skip, pool, ups>())
+                    hipLaunchKernelGGL((conv3x3_split_kernel<1, wco, pre_, b8, f32_, skip, pool, ups>), grid, dim3(CV_THREADS), 0, st, a);
+                else return conv_not_built();
+                return 0;
+            }, pre, in_b8, f32, a.skip_in != nullptr, a.resample == 1, a.resample == 2);
+        })) return e;
+    SLR_CHECK_LAUNCH();
+    if (a.resample == 2) {                              // the up-sampling epilogue's tile borders
+        const int items = 2 * a.tiles_y * 2 * a.W + 2 * a.tiles_x * 2 * a.H;
+        hipLaunchKernelGGL(upsample_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
+                           (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
+        SLR_CHECK_LAUNCH();
+    } else if (a.resample == 1) {                       // ... the pooling epilogue's
+        const int OH = (a.H - 1) / 2 + 1, OW = (a.W - 1) / 2 + 1;
+        const int items = (a.tiles_y - 1) * OW + (a.tiles_x - 1) * OH;
+        if (items > 0) {
+            hipLaunchKernelGGL(pool_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
+                               (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
+            SLR_CHECK_LAUNCH();
+        }
+    }
+    return 0;
+}
+
+// ConvArgs of the six 3x3 entry points.  partial: the partial convolution (bias required; mask == NULL: derived from x != 0, needs the
+// prologue); the plain one passes no mask, next-BN or update mask.  sk: the fused skip branch or the skip output, or NULL.
+static int conv3x3_run(bool partial, const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
+                       const void *wsplit, float wscale, float xscale, const float *bias, const float *residual,
+                       const float *next_scale, const float *next_shift, float *out, float *um_out,
+                       int N, int Cin, int Cout, int H, int W, const SkipOp *sk, int layout, void *stream) {
+    SLR_CHECK_ARG(x && wsplit && (bias || !partial) && out, "null pointer");
+    if (int e = conv_check_layout(layout, x, out, Cin, Cout, residual, partial && !mask)) return e;
     SLR_CHECK_ARG(!pre_scale == !pre_shift, "pre_scale / pre_shift go together");
     SLR_CHECK_ARG(!pre_scale || Cin <= CV_MAXCIN, "prologue supports Cin <= 1024");
+    SLR_CHECK_ARG(!partial || mask || pre_scale, "mask = NULL (derived from x != 0) needs the raw input, i.e. pre_scale / pre_shift");
+    SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
+    SLR_CHECK_ARG(!(residual && next_scale), "residual and next-BN fusion are exclusive");
     if (int e = conv_check_dims(N, Cin, Cout, H, W)) return e;
     ConvArgs a = {};
-    a.in = in; a.w = (const h8 *)wsplit; a.bias = bias; a.out = out;
+    a.in = x; a.w = (const h8 *)wsplit; a.bias = bias; a.out = out;
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.pre = pre_scale ? PRE_BN : PRE_NONE;
-    a.pre_scale = pre_scale; a.pre_shift = pre_shift;
-    a.residual = residual;
+    a.pre = !pre_scale ? PRE_NONE : !partial ? PRE_BN : mask ? PRE_BN_MASK : PRE_BN_NONZERO;
+    a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.mask = mask;
+    if (partial) {
+        a.partial = 1;
+        a.mask_scale = mask ? (float)Cin : 1.0f;       // channel-uniform mask: Cin identical planes (partialconv2d.py:61)
+        a.winsize = (float)Cin * 9.0f;
+    }
+    a.residual = residual; a.next_scale = next_scale; a.next_shift = next_shift; a.um_out = um_out;
     a.out_b8 = (layout & SLR_CONV_OUT_B8) != 0;
     a.res_b8 = (layout & SLR_CONV_RES_B8) != 0;
     if (int e = conv_set_skip(a, sk, xscale, layout)) return e;
-    return conv_launch(a, wscale, xscale, (layout & SLR_CONV_IN_B8) != 0, (layout & SLR_CONV_F32) != 0, (hipStream_t)stream, (layout & SLR_CONV_WINO) != 0);
+    return conv_launch(a, wscale, xscale, layout, (hipStream_t)stream);
 }
 
 SLR_EXPORT int slr_conv3x3_forward(const float *in, const void *wsplit, const float *bias, const float *residual,
                                    float *out, int N, int Cin, int Cout, int H, int W, float wscale, float xscale,
                                    const float *pre_scale, const float *pre_shift, int layout, void *stream) {
-    return conv3x3_forward_impl(in, wsplit, bias, residual, out, N, Cin, Cout, H, W, wscale, xscale, pre_scale, pre_shift, nullptr, layout, stream);
+    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
+                       N, Cin, Cout, H, W, nullptr, layout, stream);
 }
 
 SLR_EXPORT int slr_conv3x3_forward_skip(const float *in, const void *wsplit, const float *bias, float *out,
@@ -1559,7 +1520,8 @@ SLR_EXPORT int slr_conv3x3_forward_skip(const float *in, const void *wsplit, con
                                         const float *skip_in, const void *skip_wsplit, const float *skip_bias, int skip_cin, float skip_wscale,
                                         void *pool_ws, size_t pool_ws_bytes, int layout, void *stream) {
     const SkipOp sk = {skip_in, skip_wsplit, skip_bias, skip_cin, skip_wscale, pool_ws, pool_ws_bytes, nullptr};
-    return conv3x3_forward_impl(in, wsplit, bias, nullptr, out, N, Cin, Cout, H, W, wscale, xscale, pre_scale, pre_shift, &sk, layout, stream);
+    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, nullptr,
+                       N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
 SLR_EXPORT int slr_conv3x3_forward_skipout(const float *in, const void *wsplit, const float *bias, const float *residual, float *out,
@@ -1568,42 +1530,16 @@ SLR_EXPORT int slr_conv3x3_forward_skipout(const float *in, const void *wsplit, 
                                            const float *skip_w4, const float *skip_bias, float *skip_out, int layout, void *stream) {
     SLR_CHECK_ARG(skip_w4 && skip_out, "null pointer");
     const SkipOp sk = {nullptr, skip_w4, skip_bias, 0, 1.0f, nullptr, 0, skip_out};
-    return conv3x3_forward_impl(in, wsplit, bias, residual, out, N, Cin, Cout, H, W, wscale, xscale, pre_scale, pre_shift, &sk, layout, stream);
-}
-
-static int pconv3x3_forward_impl(const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
-                                    const void *wsplit, float wscale, float xscale, const float *bias, const float *residual,
-                                    const float *next_scale, const float *next_shift, float *out, float *um_out,
-                                    int N, int Cin, int Cout, int H, int W, const SkipOp *sk, int layout, void *stream) {
-    SLR_CHECK_ARG(x && wsplit && bias && out, "null pointer");
-    if (int e = conv_check_layout(layout, x, out, Cin, Cout, residual, mask == nullptr)) return e;
-    SLR_CHECK_ARG(!pre_scale == !pre_shift, "pre_scale / pre_shift go together");
-    SLR_CHECK_ARG(!pre_scale || Cin <= CV_MAXCIN, "prologue supports Cin <= 1024");
-    SLR_CHECK_ARG(mask || pre_scale, "mask = NULL (derived from x != 0) needs the raw input, i.e. pre_scale / pre_shift");
-    SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
-    SLR_CHECK_ARG(!(residual && next_scale), "residual and next-BN fusion are exclusive");
-    if (int e = conv_check_dims(N, Cin, Cout, H, W)) return e;
-    ConvArgs a = {};
-    a.in = x; a.w = (const h8 *)wsplit; a.bias = bias; a.out = out;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.pre = !pre_scale ? PRE_NONE : (mask ? PRE_BN_MASK : PRE_BN_NONZERO);
-    a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.mask = mask;
-    a.partial = 1;
-    a.mask_scale = mask ? (float)Cin : 1.0f;           // channel-uniform mask: Cin identical planes (partialconv2d.py:61)
-    a.winsize = (float)Cin * 9.0f;
-    a.residual = residual; a.next_scale = next_scale; a.next_shift = next_shift; a.um_out = um_out;
-    a.out_b8 = (layout & SLR_CONV_OUT_B8) != 0;
-    a.res_b8 = (layout & SLR_CONV_RES_B8) != 0;
-    if (int e = conv_set_skip(a, sk, xscale, layout)) return e;
-    return conv_launch(a, wscale, xscale, (layout & SLR_CONV_IN_B8) != 0, (layout & SLR_CONV_F32) != 0, (hipStream_t)stream, (layout & SLR_CONV_WINO) != 0);
+    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
+                       N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
 SLR_EXPORT int slr_pconv3x3_forward(const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
                                     const void *wsplit, float wscale, float xscale, const float *bias, const float *residual,
                                     const float *next_scale, const float *next_shift, float *out, float *um_out,
                                     int N, int Cin, int Cout, int H, int W, int layout, void *stream) {
-    return pconv3x3_forward_impl(x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
-                                 N, Cin, Cout, H, W, nullptr, layout, stream);
+    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
+                       N, Cin, Cout, H, W, nullptr, layout, stream);
 }
 
 SLR_EXPORT int slr_pconv3x3_forward_skip(const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
@@ -1612,8 +1548,8 @@ SLR_EXPORT int slr_pconv3x3_forward_skip(const float *x, const float *pre_scale,
                                          const float *skip_in, const void *skip_wsplit, int skip_cin, float skip_wscale,
                                          void *pool_ws, size_t pool_ws_bytes, int layout, void *stream) {
     const SkipOp sk = {skip_in, skip_wsplit, nullptr, skip_cin, skip_wscale, pool_ws, pool_ws_bytes, nullptr};
-    return pconv3x3_forward_impl(x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, um_out,
-                                 N, Cin, Cout, H, W, &sk, layout, stream);
+    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, um_out,
+                       N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
 SLR_EXPORT int slr_pconv3x3_forward_skipout(const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
@@ -1623,6 +1559,6 @@ SLR_EXPORT int slr_pconv3x3_forward_skipout(const float *x, const float *pre_sca
                                             const float *skip_w4, float *skip_out, int layout, void *stream) {
     SLR_CHECK_ARG(skip_w4 && skip_out, "null pointer");
     const SkipOp sk = {nullptr, skip_w4, nullptr, 0, 1.0f, nullptr, 0, skip_out};
-    return pconv3x3_forward_impl(x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
-                                 N, Cin, Cout, H, W, &sk, layout, stream);
+    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
+                       N, Cin, Cout, H, W, &sk, layout, stream);
 }

@@ -20,7 +20,10 @@ Own definitions, folded for inference (reference file:line cited 
 
 ``load_reference_state_dict`` maps the reference's checkpoint key scheme onto these modules.
 """
+import collections
+import ctypes
 import math
+import types
 
 import threading
 
@@ -142,12 +145,28 @@ class staged_skips:
         return False
 
 
-def _skip_rides(a, cout, b8, b8_in):
-    """The skip branch can ride in the second 3x3 kernel: split-f16 rung, channel-blocked block input and intermediate, more than 4
-    output channels (include/slr_splat.h: slr_conv3x3_forward_skip)."""
-    if _S.f32_kernels and (_S.winograd or cout <= 64):         # fp32 rung: the 128-channel kernels only; none in the Winograd kernel
-        return False
-    return bool(_S.fused_skips and b8 and b8_in and cout > 4 and a.is_cuda and not _S.torch_convs)
+_BlockRoute = collections.namedtuple("_BlockRoute", "form b8 first skip second pool")
+
+
+def _block_route(blk, x, b8_in, explicit_mask=True):
+    """How a residual block (ResBlock, PconvResBlock) runs on ``x``: form "narrow" (<= 4 output channels: the first 3x3 kernel also
+    writes the skip conv_b(x), slr_*_forward_skipout; needs an explicit mask), "fused" (the skip rides in the second 3x3 kernel,
+    slr_*_forward_skip: channel-blocked block input and intermediate, more than 4 output channels; on the fp32 rung the 128-channel
+    kernels only, none in the Winograd kernel) or "staged" (1x1 kernel -> residual of the second 3x3 kernel); ``b8``: the block's
+    output is channel-blocked (see _b8); the layout flags of the ``first`` 3x3, the ``skip`` 1x1 (staged) and the ``second`` 3x3
+    kernel; ``pool``: the resampling the fused second kernel takes into its epilogue (False, True = "Down", "Up")."""
+    cout = blk.conv_aa.weight.shape[0]
+    b8 = _b8(x, cout)                                   # layout of everything the block produces
+    lin = IN_B8 if b8_in else 0
+    rides = blk.conv_b is not None and b8_in and _S.fused_skips and x.is_cuda and not _S.torch_convs
+    if rides and cout <= 4 and explicit_mask:           # the narrow end (128 -> 3): conv_aa and conv_b(x) from one pass over x
+        return _BlockRoute("narrow", b8, lin, 0, 0, False)
+    first = lin | (OUT_B8 if b8 else 0)
+    if rides and b8 and cout > 4 and not (_S.f32_kernels and (_S.winograd or cout <= 64)):
+        return _BlockRoute("fused", b8, first, 0, IN_B8 | OUT_B8, blk.pools if (cout > 64 and _S.fused_pools) else False)
+    skip_b8 = b8 and cout > 4 if blk.conv_b is not None else b8_in          # (the <= 4-channel skip kernel writes NCHW)
+    second = (IN_B8 | OUT_B8 if b8 else 0) | (RES_B8 if skip_b8 and b8 else 0)
+    return _BlockRoute("staged", b8, first, lin | (OUT_B8 if skip_b8 else 0), second, False)
 
 
 def _pool_out(N, cout, H, W, like, pool):
@@ -200,16 +219,30 @@ def _fused_ok(*ts):
     return True
 
 
+def _call(name, device, *args):
+    """Entry point ``name`` of the library, looked up at every call, with ``args`` (tensors as their device pointers) and torch's
+    current stream on ``device``, run with ``device`` current; raises naming the entry point if it fails."""
+    args = [_lib.ptr(a) if torch.is_tensor(a) else a for a in args]
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), name)
+
+
+def _cached(owner, name, make, *tensors):
+    """``make()``, kept in ``owner.__dict__[name]`` while ``tensors`` (what the value is derived from) keep their (data_ptr, _version,
+    device): a move to another device, an in-place update (``load_state_dict``, ``copy_``) or a new tensor makes it again."""
+    key = tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+    c = owner.__dict__.get(name)
+    if c is None or c[0] != key:
+        c = owner.__dict__[name] = (key, make())
+    return c[1]
+
+
 def bn_relu_mask(x, scale, shift, mask):
     """relu(x*scale - shift) * mask;  mask None = (x != 0), mask False = no mask."""
     if _fused_ok(x, *([mask] if torch.is_tensor(mask) else [])):
-        N, C, H, W = x.shape
         y = torch.empty_like(x)
         mc = -1 if mask is False else 0 if mask is None else mask.shape[1]
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_bn_relu_mask(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift),
-                                                   _lib.ptr(mask) if torch.is_tensor(mask) else None, mc, _lib.ptr(y),
-                                                   N, C, H, W, _lib.stream_of(x)), "slr_bn_relu_mask")
+        _call("slr_bn_relu_mask", x.device, x, scale, shift, mask if torch.is_tensor(mask) else None, mc, y, *x.shape)
         return y
     y = F.relu(x * scale.view(1, -1, 1, 1) - shift.view(1, -1, 1, 1))
     if mask is False:
@@ -222,15 +255,11 @@ def pconv_epilogue(raw0, bias, mask_box, mask_scale, winsize, residual=None, nex
     convolution's relu(bn(.))*um  (partialconv2d.py:61-74, blocks.py:233-236,248).
     um_raw = mask_box*mask_scale.  Returns (out, um)."""
     if _fused_ok(raw0, mask_box, *([] if residual is None else [residual])):
-        N, C, H, W = raw0.shape
         out = torch.empty_like(raw0)
         um = torch.empty_like(mask_box)
         sc, sh = next_bn if next_bn is not None else (None, None)
-        with torch.cuda.device(raw0.device):
-            _lib.check(_lib.lib().slr_pconv_epilogue(_lib.ptr(raw0), _lib.ptr(bias), _lib.ptr(mask_box), float(mask_scale),
-                                                     _lib.ptr(residual), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(out),
-                                                     _lib.ptr(um), float(winsize), N, C, H, W,
-                                                     _lib.stream_of(raw0)), "slr_pconv_epilogue")
+        _call("slr_pconv_epilogue", raw0.device, raw0, bias, mask_box, float(mask_scale), residual, sc, sh, out, um, float(winsize),
+              *raw0.shape)
         return out, um
     um_raw = mask_box * mask_scale
     um = torch.clamp(um_raw, 0, 1)
@@ -256,13 +285,11 @@ class AffineBN(nn.Module):
         self.register_buffer("stored_var", torch.ones(ch))
 
     def scale_shift(self):
-        """(scale, shift), computed once per device (statistics are frozen at inference; loading a
-        state dict resets the cache)."""
-        c = self.__dict__.get("_ss")
-        if c is None or c[0].device != self.stored_var.device:
+        """(scale, shift), computed once per device and version of the statistics."""
+        def make():
             scale = torch.rsqrt(self.stored_var + self.eps)
-            c = self.__dict__["_ss"] = (scale, self.stored_mean * scale)
-        return c
+            return scale, self.stored_mean * scale
+        return _cached(self, "_ss", make, self.stored_mean, self.stored_var)
 
     def forward(self, x):
         scale, shift = self.scale_shift()
@@ -287,46 +314,58 @@ class Conv(nn.Module):
         """This 1x1 convolution's weights as plain fp32 [Cin][4] (row ci = w[0..3][ci], zero padded): the skip operand of the <= 4-channel
         3x3 kernel (slr_*_forward_skipout); prepared once per device / weight version."""
         w = self.weight
-        key = (w.data_ptr(), w._version, w.device)
-        c = self.__dict__.get("_w4c")
-        if c is None or c[0] != key:
+
+        def make():
             w4 = torch.zeros(w.shape[1], 4, device=w.device, dtype=torch.float32)
             w4[:, :w.shape[0]] = w.view(w.shape[0], w.shape[1]).t()
-            c = self.__dict__["_w4c"] = (key, w4.contiguous())
-        return c[1]
+            return w4.contiguous()
+        return _cached(self, "_w4c", make, w)
+
+    def _conv3x3(self, name, x, args, layout=0, pre_bn=None, next_bn=None, partial=False, skipout=False, skip_conv=None,
+                 skip_b8=False, pool=False):
+        """The device path of the six 3x3 methods (conv, forward_skip, forward_skipout; PartialConv's forward, forward_skip,
+        forward_skipout): weights and rung flags, outputs, the call of entry point ``name`` and its check.  ``args(c)`` puts the
+        entry point's arguments before ``layout`` in its order, from ``c``: buf, wscale, xscale (the weights), psc, psh / nsc, nsh
+        (``pre_bn`` / ``next_bn``), out, um (the update mask of a ``partial`` convolution), skip (the ``skipout`` forms' skip result),
+        dims = (N, Cin, Cout, H, W); with ``skip_conv`` (the fused skip forms) sbuf, swscale, ws, ws_bytes: the skip's weights and the
+        pooling scratch of ``pool``.  Returns ``c``."""
+        N, cin, H, W = x.shape
+        cout = self.weight.shape[0]
+        c = types.SimpleNamespace(dims=(N, cin, cout, H, W), um=None, skip=None)
+        c.buf, c.wscale, c.xscale, arith = self._split_weights()
+        c.psc, c.psh = pre_bn if pre_bn is not None else (None, None)
+        c.nsc, c.nsh = next_bn if next_bn is not None else (None, None)
+        layout |= arith
+        if skip_conv is not None:
+            c.sbuf, c.swscale, _, sarith = skip_conv._split_weights()
+            assert arith == sarith and not (arith & CONV_WINO)
+            c.out, c.ws, c.ws_bytes, pflag = _pool_out(N, cout, H, W, x, pool)
+            layout |= pflag | (SKIP_B8 if skip_b8 else 0)
+        else:
+            c.out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
+        if skipout:
+            c.skip = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
+        if partial:
+            c.um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
+        _call(name, x.device, *args(c), layout)
+        return c
 
     def forward_skipout(self, x, pre_bn, skip_conv, layout=0):
         """(conv(relu(bn(x))) + bias, skip_conv(x)) from ONE pass over x: Cout <= 4, channel-blocked x (slr_conv3x3_forward_skipout)."""
         assert self.k == 3 and skip_conv.k == 1 and _fused_ok(x)
-        cout, cin = self.weight.shape[:2]
-        N, _, H, W = x.shape
-        buf, wscale, xscale, arith = self._split_weights()
-        out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-        skip = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-        sc, sh = pre_bn if pre_bn is not None else (None, None)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_conv3x3_forward_skipout(
-                _lib.ptr(x), _lib.ptr(buf), _lib.ptr(self.bias), None, _lib.ptr(out), N, cin, cout, H, W, wscale, xscale, _lib.ptr(sc), _lib.ptr(sh),
-                _lib.ptr(skip_conv._w4()), _lib.ptr(skip_conv.bias), _lib.ptr(skip), layout | arith, _lib.stream_of(x)), "slr_conv3x3_forward_skipout")
-        return out, skip
+        c = self._conv3x3("slr_conv3x3_forward_skipout", x, lambda c: (
+            x, c.buf, self.bias, None, c.out, *c.dims, c.wscale, c.xscale, c.psc, c.psh, skip_conv._w4(), skip_conv.bias, c.skip),
+            layout, pre_bn, skipout=True)
+        return c.out, c.skip
 
     def forward_skip(self, x, pre_bn, skip_x, skip_conv, layout=0, skip_b8=False, pool=False):
         """conv(relu(bn(x))) + bias + skip_conv(skip_x) in ONE kernel (slr_conv3x3_forward_skip; blocks.py:83-87); ``pool``: and the
         "Down" block's average pool (:196-199) in its epilogue."""
         assert self.k == 3 and skip_conv.k == 1 and _fused_ok(x, skip_x)
-        cout, cin = self.weight.shape[:2]
-        N, _, H, W = x.shape
-        buf, wscale, xscale, arith = self._split_weights()
-        sbuf, swscale, _, sarith = skip_conv._split_weights()
-        assert arith == sarith and not (arith & CONV_WINO)
-        out, ws, ws_bytes, pflag = _pool_out(N, cout, H, W, x, pool)
-        sc, sh = pre_bn if pre_bn is not None else (None, None)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_conv3x3_forward_skip(
-                _lib.ptr(x), _lib.ptr(buf), _lib.ptr(self.bias), _lib.ptr(out), N, cin, cout, H, W, wscale, xscale, _lib.ptr(sc), _lib.ptr(sh),
-                _lib.ptr(skip_x), _lib.ptr(sbuf), _lib.ptr(skip_conv.bias), skip_x.shape[1], swscale, _lib.ptr(ws), ws_bytes,
-                layout | arith | pflag | (SKIP_B8 if skip_b8 else 0), _lib.stream_of(x)), "slr_conv3x3_forward_skip")
-        return out
+        return self._conv3x3("slr_conv3x3_forward_skip", x, lambda c: (
+            x, c.buf, self.bias, c.out, *c.dims, c.wscale, c.xscale, c.psc, c.psh,
+            skip_x, c.sbuf, skip_conv.bias, skip_x.shape[1], c.swscale, c.ws, c.ws_bytes),
+            layout, pre_bn, skip_conv=skip_conv, skip_b8=skip_b8, pool=pool).out
 
     def _split_weights(self):
         """Weights of the matrix-core kernels (csrc/conv.hip) in fragment order, prepared once per device / weight version and
@@ -335,29 +374,22 @@ class Conv(nn.Module):
         w = self.weight
         f32 = _S.f32_kernels
         wino = f32 and _S.winograd and self.k == 3 and w.shape[0] > 4 and w.shape[1] <= 256     # (its prologue table holds 256 channels)
-        key = (w.data_ptr(), w._version, w.device)
-        name = "_wwino" if wino else "_wf32" if f32 else "_wsplit"
-        c = self.__dict__.get(name)
-        if c is None or c[0] != key:
-            L = _lib.lib()
-            nbytes = L.slr_conv3x3_wino_weight_bytes if wino else L.slr_conv3x3_weight_bytes if self.k == 3 else L.slr_conv1x1_weight_bytes
+        kind = "wino" if wino else "f32" if f32 else "split"
+        conv = "conv3x3" if self.k == 3 else "conv1x1"
+
+        def make():
+            nbytes = getattr(_lib.lib(), "slr_conv3x3_wino_weight_bytes" if wino else f"slr_{conv}_weight_bytes")
             buf = torch.empty(nbytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
-            with torch.cuda.device(w.device):
-                if wino:
-                    wscale = 1.0
-                    _lib.check(L.slr_conv3x3_wino_weights(_lib.ptr(w), _lib.ptr(buf), w.shape[0], w.shape[1], _lib.stream_of(w)), "slr_conv3x3_wino_weights")
-                elif f32:
-                    prep = L.slr_conv3x3_f32_weights if self.k == 3 else L.slr_conv1x1_f32_weights
-                    wscale = 1.0
-                    _lib.check(prep(_lib.ptr(w), _lib.ptr(buf), w.shape[0], w.shape[1], _lib.stream_of(w)), "slr_conv_f32_weights")
-                else:
-                    amax = float(w.abs().max())
-                    wscale = 2.0 ** math.floor(math.log2(4096.0 / amax)) if amax > 0 else 1.0
-                    split = L.slr_conv3x3_split_weights if self.k == 3 else L.slr_conv1x1_split_weights
-                    _lib.check(split(_lib.ptr(w), _lib.ptr(buf), w.shape[0], w.shape[1], wscale, _lib.stream_of(w)),
-                               "slr_conv_split_weights")
-            c = self.__dict__[name] = (key, buf, wscale)
-        return (c[1], 1.0, 1.0, CONV_F32 | (CONV_WINO if wino else 0)) if f32 else (c[1], c[2], _S.act_scale, 0)
+            if f32:
+                wscale = 1.0
+                _call(f"slr_{conv}_{'wino' if wino else 'f32'}_weights", w.device, w, buf, w.shape[0], w.shape[1])
+            else:
+                amax = float(w.abs().max())
+                wscale = 2.0 ** math.floor(math.log2(4096.0 / amax)) if amax > 0 else 1.0
+                _call(f"slr_{conv}_split_weights", w.device, w, buf, w.shape[0], w.shape[1], wscale)
+            return buf, wscale
+        buf, wscale = _cached(self, "_w" + kind, make, w)
+        return (buf, 1.0, 1.0, CONV_F32 | (CONV_WINO if wino else 0)) if f32 else (buf, wscale, _S.act_scale, 0)
 
     def conv(self, x, bias, pre_bn=None, residual=None, layout=0):
         """conv(relu(bn(x))) + bias + residual (``pre_bn`` = (scale, shift) of the BN in front, or None).
@@ -366,16 +398,8 @@ class Conv(nn.Module):
         tensors (validation against the reference classes, inside nets.cpu_reference()) take the torch
         composition."""
         if self.k == 3 and _fused_ok(x, *([] if residual is None else [residual])):
-            cout, cin = self.weight.shape[:2]
-            N, _, H, W = x.shape
-            buf, wscale, xscale, arith = self._split_weights()
-            out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-            sc, sh = pre_bn if pre_bn is not None else (None, None)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().slr_conv3x3_forward(_lib.ptr(x), _lib.ptr(buf), _lib.ptr(bias), _lib.ptr(residual), _lib.ptr(out),
-                                                          N, cin, cout, H, W, wscale, xscale, _lib.ptr(sc), _lib.ptr(sh),
-                                                          layout | arith, _lib.stream_of(x)), "slr_conv3x3_forward")
-            return out
+            return self._conv3x3("slr_conv3x3_forward", x, lambda c: (
+                x, c.buf, bias, residual, c.out, *c.dims, c.wscale, c.xscale, c.psc, c.psh), layout, pre_bn).out
         assert layout == 0 or x.is_cuda        # the channel-blocked intermediate exists on the device path only
         if residual is not None:
             return self.conv(x, bias, pre_bn) + residual
@@ -386,21 +410,15 @@ class Conv(nn.Module):
             N, cin, H, W = x.shape                      # skip branch onto the 3 output channels: HBM-bound HIP kernel
             cout = self.weight.shape[0]
             out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-            with torch.cuda.device(x.device):
-                assert not (layout & OUT_B8)
-                _lib.check(_lib.lib().slr_conv1x1_small(_lib.ptr(x), _lib.ptr(self.weight), _lib.ptr(bias), _lib.ptr(out),
-                                                        N, cin, cout, H, W, int(bool(layout & IN_B8)), _lib.stream_of(x)),
-                           "slr_conv1x1_small")
+            assert not (layout & OUT_B8)
+            _call("slr_conv1x1_small", x.device, x, self.weight, bias, out, N, cin, cout, H, W, int(bool(layout & IN_B8)))
             return out
         if self.k == 1 and _fused_ok(x):                 # the other 1x1 skip branches: split-f16 MFMA, HBM-bound
             N, cin, H, W = x.shape
             cout = self.weight.shape[0]
             buf, wscale, xscale, arith = self._split_weights()
             out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().slr_conv1x1_forward(_lib.ptr(x), _lib.ptr(buf), _lib.ptr(bias), _lib.ptr(out),
-                                                          N, cin, cout, H, W, wscale, xscale, layout | arith, _lib.stream_of(x)),
-                           "slr_conv1x1_forward")
+            _call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, wscale, xscale, layout | arith)
             return out
         return F.conv2d(x, self.weight, bias, padding=self.pad)
 
@@ -425,58 +443,29 @@ class PartialConv(Conv):
         """The block's first partial convolution and, from the same pass over x, the block's 1x1 skip convolution of the raw x: Cout <= 4,
         channel-blocked x (slr_pconv3x3_forward_skipout; blocks.py:229-236, 243-247).  Returns (out, update_mask, skip)."""
         assert self.k == 3 and skip_conv.k == 1 and skip_conv.bias is None and _fused_ok(x, *([] if mask is None else [mask]))
-        cin = x.shape[1]
-        N, _, H, W = x.shape
-        cout = self.weight.shape[0]
-        buf, wscale, xscale, arith = self._split_weights()
-        out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-        skip = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-        um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
-        psc, psh = pre_bn if pre_bn is not None else (None, None)
-        nsc, nsh = next_bn if next_bn is not None else (None, None)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_pconv3x3_forward_skipout(
-                _lib.ptr(x), _lib.ptr(psc), _lib.ptr(psh), _lib.ptr(mask), _lib.ptr(buf), wscale, xscale, _lib.ptr(self.bias), None,
-                _lib.ptr(nsc), _lib.ptr(nsh), _lib.ptr(out), _lib.ptr(um), N, cin, cout, H, W,
-                _lib.ptr(skip_conv._w4()), _lib.ptr(skip), layout | arith, _lib.stream_of(x)), "slr_pconv3x3_forward_skipout")
-        return out, um, skip
+        c = self._conv3x3("slr_pconv3x3_forward_skipout", x, lambda c: (
+            x, c.psc, c.psh, mask, c.buf, c.wscale, c.xscale, self.bias, None, c.nsc, c.nsh, c.out, c.um, *c.dims,
+            skip_conv._w4(), c.skip), layout, pre_bn, next_bn, partial=True, skipout=True)
+        return c.out, c.um, c.skip
 
     def forward_skip(self, x, mask, skip_x, skip_conv, layout=0, skip_b8=False, pool=False):
         """The block's second partial convolution with the 1x1 skip branch inside (slr_pconv3x3_forward_skip; blocks.py:237-248):
         ``x`` is the activated, masked output of the first one.  Returns (out, update_mask)."""
         assert self.k == 3 and skip_conv.k == 1 and skip_conv.bias is None and _fused_ok(x, mask, skip_x)
-        cin = x.shape[1]
-        N, _, H, W = x.shape
-        cout = self.weight.shape[0]
-        buf, wscale, xscale, arith = self._split_weights()
-        sbuf, swscale, _, sarith = skip_conv._split_weights()
-        assert arith == sarith and not (arith & CONV_WINO)
-        out, ws, ws_bytes, pflag = _pool_out(N, cout, H, W, x, pool)
-        um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_pconv3x3_forward_skip(
-                _lib.ptr(x), None, None, _lib.ptr(mask), _lib.ptr(buf), wscale, xscale, _lib.ptr(self.bias), _lib.ptr(out), _lib.ptr(um),
-                N, cin, cout, H, W, _lib.ptr(skip_x), _lib.ptr(sbuf), skip_x.shape[1], swscale, _lib.ptr(ws), ws_bytes,
-                layout | arith | pflag | (SKIP_B8 if skip_b8 else 0), _lib.stream_of(x)), "slr_pconv3x3_forward_skip")
-        return out, um
+        c = self._conv3x3("slr_pconv3x3_forward_skip", x, lambda c: (
+            x, None, None, mask, c.buf, c.wscale, c.xscale, self.bias, c.out, c.um, *c.dims,
+            skip_x, c.sbuf, skip_x.shape[1], c.swscale, c.ws, c.ws_bytes),
+            layout, partial=True, skip_conv=skip_conv, skip_b8=skip_b8, pool=pool)
+        return c.out, c.um
 
     def forward(self, x, mask, residual=None, next_bn=None, pre_bn=None, layout=0):
         cin = x.shape[1]
         assert mask is not None or pre_bn is not None
         if self.k == 3 and _fused_ok(x, *([] if mask is None else [mask]), *([] if residual is None else [residual])):
-            N, _, H, W = x.shape
-            cout = self.weight.shape[0]
-            buf, wscale, xscale, arith = self._split_weights()
-            out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-            um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
-            psc, psh = pre_bn if pre_bn is not None else (None, None)
-            nsc, nsh = next_bn if next_bn is not None else (None, None)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().slr_pconv3x3_forward(
-                    _lib.ptr(x), _lib.ptr(psc), _lib.ptr(psh), _lib.ptr(mask), _lib.ptr(buf), wscale, xscale,
-                    _lib.ptr(self.bias), _lib.ptr(residual), _lib.ptr(nsc), _lib.ptr(nsh), _lib.ptr(out), _lib.ptr(um),
-                    N, cin, cout, H, W, layout | arith, _lib.stream_of(x)), "slr_pconv3x3_forward")
-            return out, um
+            c = self._conv3x3("slr_pconv3x3_forward", x, lambda c: (
+                x, c.psc, c.psh, mask, c.buf, c.wscale, c.xscale, self.bias, residual, c.nsc, c.nsh, c.out, c.um, *c.dims),
+                layout, pre_bn, next_bn, partial=True)
+            return c.out, c.um
         assert layout == 0
         if mask is None:
             mplane, mscale = (x != 0).sum(1, keepdim=True).to(x.dtype), 1.0
@@ -493,9 +482,7 @@ def avgpool_down(x, b8=False):
     if _fused_ok(x):
         N, C, H, W = x.shape
         out = torch.empty(N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_avgpool3x3s2(_lib.ptr(x), _lib.ptr(out), N, C, H, W, int(b8), _lib.stream_of(x)),
-                       "slr_avgpool3x3s2")
+        _call("slr_avgpool3x3s2", x.device, x, out, N, C, H, W, int(b8))
         return out
     return F.avg_pool2d(x, 3, stride=2, padding=1)
 
@@ -505,9 +492,7 @@ def upsample_up(x, b8=False):
     if _fused_ok(x):
         N, C, H, W = x.shape
         out = torch.empty(N, C, 2 * H, 2 * W, device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_upsample_bilinear2x(_lib.ptr(x), _lib.ptr(out), N, C, H, W, int(b8), _lib.stream_of(x)),
-                       "slr_upsample_bilinear2x")
+        _call("slr_upsample_bilinear2x", x.device, x, out, N, C, H, W, int(b8))
         return out
     return F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
 
@@ -541,27 +526,18 @@ class ResBlock(nn.Module):
 
     def forward(self, x, b8_in=False):
         """-> (y, b8_out): ``b8_in`` / ``b8_out`` = x / y are channel-blocked in memory (see _b8)."""
-        cout = self.conv_aa.weight.shape[0]
-        b8 = _b8(x, cout)                                   # layout of everything this block produces
-        lin = IN_B8 if b8_in else 0
-        if self.conv_b is not None and cout <= 4 and b8_in and _S.fused_skips and x.is_cuda and not _S.torch_convs:
-            # the narrow end (128 -> 3): conv_aa and the skip conv_b(x) from one pass over x
-            a, b = self.conv_aa.forward_skipout(x, self.bn1.scale_shift(), self.conv_b, layout=lin)
+        r = _block_route(self, x, b8_in)
+        if r.form == "narrow":
+            a, b = self.conv_aa.forward_skipout(x, self.bn1.scale_shift(), self.conv_b, layout=r.first)
             a = self.conv_ab(a, self.bn2.scale_shift(), residual=b)
-            return self.resample(a, b8), b8
-        a = self.conv_aa(x, self.bn1.scale_shift(), layout=lin | (OUT_B8 if b8 else 0))   # BN + ReLU ride in the prologue
-        if self.conv_b is not None and _skip_rides(a, cout, b8, b8_in):                        # x_a + conv_b(x) (:83-87) in one kernel
-            pool = self.pools if (cout > 64 and _S.fused_pools) else False
-            a = self.conv_ab.forward_skip(a, self.bn2.scale_shift(), x, self.conv_b, layout=IN_B8 | OUT_B8, skip_b8=b8_in, pool=pool)
-            return (a if pool else self.resample(a, b8)), b8
-        if self.conv_b is not None:
-            skip_b8 = b8 and cout > 4                       # (the <= 4-channel skip kernel writes NCHW)
-            b = self.conv_b(x, layout=lin | (OUT_B8 if skip_b8 else 0))
-        else:
-            b, skip_b8 = x, b8_in
-        a = self.conv_ab(a, self.bn2.scale_shift(), residual=b,                           # x_a + x_b (:87) in the epilogue
-                         layout=(IN_B8 if b8 else 0) | (OUT_B8 if b8 else 0) | (RES_B8 if skip_b8 and b8 else 0))
-        return self.resample(a, b8), b8       # == resample(x_a) + resample(x_b): both resamplers are linear
+            return self.resample(a, r.b8), r.b8
+        a = self.conv_aa(x, self.bn1.scale_shift(), layout=r.first)                         # BN + ReLU ride in the prologue
+        if r.form == "fused":                                                                # x_a + conv_b(x) (:83-87) in one kernel
+            a = self.conv_ab.forward_skip(a, self.bn2.scale_shift(), x, self.conv_b, layout=r.second, skip_b8=b8_in, pool=r.pool)
+            return (a if r.pool else self.resample(a, r.b8)), r.b8
+        b = self.conv_b(x, layout=r.skip) if self.conv_b is not None else x
+        a = self.conv_ab(a, self.bn2.scale_shift(), residual=b, layout=r.second)             # x_a + x_b (:87) in the epilogue
+        return self.resample(a, r.b8), r.b8       # == resample(x_a) + resample(x_b): both resamplers are linear
 
 
 class PconvResBlock(nn.Module):
@@ -579,31 +555,21 @@ class PconvResBlock(nn.Module):
     def forward(self, x, mask, b8_in=False):
         """-> (y, update_mask, b8_out).  mask: None = (x != 0) per channel (architectures.py:369; x is NCHW then), else
         [N,1,H,W] channel-uniform; ``b8_in`` / ``b8_out``: x / y are channel-blocked in memory (see _b8)."""
-        cout = self.conv_aa.weight.shape[0]
-        b8 = _b8(x, cout)
-        lin = IN_B8 if b8_in else 0
-        if self.conv_b is not None and cout <= 4 and b8_in and mask is not None and _S.fused_skips and x.is_cuda and not _S.torch_convs:
-            # the narrow end (128 -> 3): conv_aa and the skip conv_b(x) from one pass over x
-            a, m, skip = self.conv_aa.forward_skipout(x, mask, self.conv_b, self.bn2.scale_shift(), self.bn1.scale_shift(), layout=lin)
+        r = _block_route(self, x, b8_in, mask is not None)
+        if r.form == "narrow":
+            a, m, skip = self.conv_aa.forward_skipout(x, mask, self.conv_b, self.bn2.scale_shift(), self.bn1.scale_shift(), layout=r.first)
             a, m = self.conv_ab(a, m, residual=skip)
-            return self.resample(a, b8), self.resample_mask(m), b8
-        a, m = self.conv_aa(x, mask, next_bn=self.bn2.scale_shift(), pre_bn=self.bn1.scale_shift(),
-                            layout=lin | (OUT_B8 if b8 else 0))                      # :229-236
+            return self.resample(a, r.b8), self.resample_mask(m), r.b8
+        a, m = self.conv_aa(x, mask, next_bn=self.bn2.scale_shift(), pre_bn=self.bn1.scale_shift(), layout=r.first)   # :229-236
         # x_a + x_b (:248).  The reference resamples the two branches separately and adds; avg-pool
         # and bilinear up-sampling are linear, so resample(x_a + x_b) is the same result up to fp32
         # rounding, lets the residual join the epilogue, and halves the resampling work.
-        if self.conv_b is not None and _skip_rides(a, cout, b8, b8_in):                # :237-248 in one kernel
-            pool = self.pools if (cout > 64 and _S.fused_pools) else False
-            a, m = self.conv_ab.forward_skip(a, m, x, self.conv_b, layout=IN_B8 | OUT_B8, skip_b8=b8_in, pool=pool)
-            return (a if pool else self.resample(a, b8)), self.resample_mask(m), b8
-        if self.conv_b is not None:                                                # :243-247
-            skip_b8 = b8 and cout > 4
-            skip = self.conv_b(x, layout=lin | (OUT_B8 if skip_b8 else 0))
-        else:
-            skip, skip_b8 = x, b8_in
-        a, m = self.conv_ab(a, m, residual=skip,                                   # :237-239
-                            layout=(IN_B8 if b8 else 0) | (OUT_B8 if b8 else 0) | (RES_B8 if skip_b8 and b8 else 0))
-        return self.resample(a, b8), self.resample_mask(m), b8                     # :240-241
+        if r.form == "fused":                                                      # :237-248 in one kernel
+            a, m = self.conv_ab.forward_skip(a, m, x, self.conv_b, layout=r.second, skip_b8=b8_in, pool=r.pool)
+            return (a if r.pool else self.resample(a, r.b8)), self.resample_mask(m), r.b8
+        skip = self.conv_b(x, layout=r.skip) if self.conv_b is not None else x   # :243-247
+        a, m = self.conv_ab(a, m, residual=skip, layout=r.second)                  # :237-239
+        return self.resample(a, r.b8), self.resample_mask(m), r.b8                 # :240-241
 
 
 # --------------------------------------------------------------------------- networks
@@ -682,12 +648,8 @@ def saturation_count(device, reset=True):
     """Waves of the split-f16 kernels on ``device`` that had to clamp an activation since the last reset (|x| beyond the
     exact domain of the split, csrc/conv.hip).  The counter is one per device; the read is ordered on torch's current
     stream of that device and synchronises it with the host."""
-    import ctypes
     n = ctypes.c_ulonglong(0)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().slr_conv_saturation_count(ctypes.byref(n), 1 if reset else 0,
-                                                        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                   "slr_conv_saturation_count")
+    _call("slr_conv_saturation_count", device, ctypes.byref(n), 1 if reset else 0)
     return int(n.value)
 
 
@@ -716,11 +678,7 @@ class SaturationLog:
         self._record()                                   # the value the clip starts from
 
     def _record(self):
-        import ctypes
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().slr_conv_saturation_record(ctypes.c_void_p(self.slots.data_ptr() + 4 * self.n),
-                                                             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       "slr_conv_saturation_record")
+        _call("slr_conv_saturation_record", self.device, ctypes.c_void_p(self.slots.data_ptr() + 4 * self.n))
         self.n += 1
 
     def mark(self):
@@ -730,6 +688,17 @@ class SaturationLog:
         torch.cuda.current_stream(self.device).synchronize()
         v = self.slots[:self.n].tolist()
         return [i for i in range(self.n - 1) if v[i + 1] != v[i]]
+
+
+RUNG_SCALES = (64.0, 1.0)                # the "auto" ladder: split-f16 at these activation scales, then the fp32 rung
+RUNG_FP32 = len(RUNG_SCALES)
+
+
+def rung_context(rung):
+    """Arithmetic of the convolutions on rung ``rung`` of the "auto" ladder: 0 split-f16 at activation scale 2^6 (exact for
+    |x| < 1023), 1 split-f16 at scale 1 (|x| < 65472), RUNG_FP32 the fp32 matrix instructions (fp32_kernels(winograd=False):
+    no limit; the safety net is the strict rung)."""
+    return fp32_kernels(winograd=False) if rung >= RUNG_FP32 else activation_scale(RUNG_SCALES[rung])
 
 
 def guarded(fn, device, policy, what, owner=None):
@@ -748,19 +717,18 @@ def guarded(fn, device, policy, what, owner=None):
     assert policy == "auto", policy
     rung = getattr(owner, "_conv_rung", 0) if owner is not None else 0
     saturation_count(device)                                   # start from a clean counter
-    for r, scale in enumerate((64.0, 1.0)):
-        if r < rung:
-            continue
-        with activation_scale(scale):
+    for r in range(rung, RUNG_FP32):
+        with rung_context(r):
             out = fn()
         if saturation_count(device) == 0:
             return out
         import warnings
         warnings.warn(f"slr_sfs_amd: activations of the {what} exceed the exact range of the split-f16 convolutions at "
-                      f"activation scale {scale:g}; rendering again " + ("at scale 1" if r == 0 else "on the fp32 rung"))
+                      f"activation scale {RUNG_SCALES[r]:g}; rendering again " +
+                      (f"at scale {RUNG_SCALES[r + 1]:g}" if r + 1 < RUNG_FP32 else "on the fp32 rung"))
         if owner is not None:
             owner._conv_rung = r + 1
-    with fp32_kernels(winograd=False):                         # (the safety net is the strict rung)
+    with rung_context(RUNG_FP32):
         return fn()
 
 
@@ -780,14 +748,12 @@ def _load_bn(bn, sd, key):
     """key = '...bn' or '...pbn' of a (Partial)LinearNoiseLayer; zero noise -> gain 1, bias 0."""
     bn.stored_mean.copy_(sd[key + ".stored_mean"])
     bn.stored_var.copy_(sd[key + ".stored_var"])
-    bn.__dict__.pop("_ss", None)
 
 
 def _load_conv(conv, sd, key):
-    conv.__dict__.pop("_wsplit", None)
-    conv.weight.data.copy_(_fold_sn(sd, key))
+    conv.weight.copy_(_fold_sn(sd, key))              # (in place: the prepared weight buffers see the new version)
     if conv.bias is not None:
-        conv.bias.data.copy_(sd[key + ".bias"])
+        conv.bias.copy_(sd[key + ".bias"])
 
 
 @torch.no_grad()
@@ -862,16 +828,12 @@ class Conv4x4s2(nn.Module):
 
     def _frag(self):
         w = self.weight
-        key = (w.data_ptr(), w._version, w.device)
-        c = self.__dict__.get("_wfrag")
-        if c is None or c[0] != key:
-            L = _lib.lib()
-            buf = torch.empty(L.slr_conv4x4s2_weight_bytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
-            with torch.cuda.device(w.device):
-                _lib.check(L.slr_conv4x4s2_f32_weights(_lib.ptr(w), _lib.ptr(buf), w.shape[0], w.shape[1], _lib.stream_of(w)),
-                           "slr_conv4x4s2_f32_weights")
-            c = self.__dict__["_wfrag"] = (key, buf)
-        return c[1]
+
+        def make():
+            buf = torch.empty(_lib.lib().slr_conv4x4s2_weight_bytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
+            _call("slr_conv4x4s2_f32_weights", w.device, w, buf, w.shape[0], w.shape[1])
+            return buf
+        return _cached(self, "_wfrag", make, w)
 
     def forward(self, x, leaky=None, bn=None):
         if _fused_ok(x):
@@ -879,10 +841,8 @@ class Conv4x4s2(nn.Module):
             cout = self.weight.shape[0]
             out = torch.empty(N, cout, (H - 2) // 2 + 1, (W - 2) // 2 + 1, device=x.device, dtype=x.dtype)
             sc, sh = bn.scale_shift() if bn is not None else (None, None)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().slr_conv4x4s2_forward(_lib.ptr(x), _lib.ptr(self._frag()), _lib.ptr(self.bias), _lib.ptr(sc),
-                                                            _lib.ptr(sh), _lib.ptr(out), N, cin, cout, H, W, int(leaky is not None),
-                                                            float(leaky or 0.0), _lib.stream_of(x)), "slr_conv4x4s2_forward")
+            _call("slr_conv4x4s2_forward", x.device, x, self._frag(), self.bias, sc, sh, out, N, cin, cout, H, W, int(leaky is not None),
+                  float(leaky or 0.0))
             return out
         if leaky is not None:
             x = F.leaky_relu(x, leaky)
@@ -903,16 +863,15 @@ class BNConv3x3(Conv):
             return self.conv(x, self.bias)
         if not _fused_ok(x):
             return self.bn(F.conv2d(x, self.weight, self.bias, padding=1))
-        key = (self.weight._version, self.bn.running_var._version, self.bn.running_mean._version, self.bn.weight._version,
-               self.bn.bias._version, self.weight.device)
-        c = self.__dict__.get("_folded")
-        if c is None or c[0] != key:
+        def make():
             scale, shift = self.bn.scale_shift()
             folded = Conv(self.cin, self.weight.shape[0], 3).to(self.weight.device)
             folded.weight.data.copy_(self.weight * scale.view(-1, 1, 1, 1))
             folded.bias.data.copy_(self.bias * scale + shift)
-            c = self.__dict__["_folded"] = (key, folded)
-        return c[1].conv(x, c[1].bias)
+            return folded
+        folded = _cached(self, "_folded", make, self.weight, self.bias, self.bn.running_mean, self.bn.running_var, self.bn.weight,
+                         self.bn.bias)
+        return folded.conv(x, folded.bias)
 
 
 def instnorm_spade(x, gamma_beta, eps=1e-5):
@@ -920,9 +879,7 @@ def instnorm_spade(x, gamma_beta, eps=1e-5):
     if _fused_ok(x, gamma_beta):
         N, C, H, W = x.shape
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().slr_instnorm_spade(_lib.ptr(x), _lib.ptr(gamma_beta), _lib.ptr(out), N, C, H, W, float(eps),
-                                                     _lib.stream_of(x)), "slr_instnorm_spade")
+        _call("slr_instnorm_spade", x.device, x, gamma_beta, out, N, C, H, W, float(eps))
         return out
     C = x.shape[1]
     return F.instance_norm(x, eps=eps) * (1 + gamma_beta[:, :C]) + gamma_beta[:, C:]
@@ -934,9 +891,7 @@ def resize_segmap(seg, k, nearest_channel=3):
     if _fused_ok(seg):
         N, C, H, W = seg.shape
         out = torch.empty(N, C, H >> k, W >> k, device=seg.device, dtype=seg.dtype)
-        with torch.cuda.device(seg.device):
-            _lib.check(_lib.lib().slr_resize_segmap(_lib.ptr(seg), _lib.ptr(out), N, C, H, W, k, nearest_channel, _lib.stream_of(seg)),
-                       "slr_resize_segmap")
+        _call("slr_resize_segmap", seg.device, seg, out, N, C, H, W, k, nearest_channel)
         return out
     size = (seg.shape[2] >> k, seg.shape[3] >> k)
     parts = [F.interpolate(seg[:, :nearest_channel], size=size, mode="bilinear", align_corners=False),
@@ -957,9 +912,7 @@ def upsample2x_concat(a, b=None, nearest_channel=-1, relu=RELU_NONE):
         N, Ca, H, W = a.shape
         Cb = 0 if b is None else b.shape[1]
         out = torch.empty(N, Ca + Cb, 2 * H, 2 * W, device=a.device, dtype=a.dtype)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().slr_upsample2x_concat(_lib.ptr(a), Ca, _lib.ptr(b), Cb, _lib.ptr(out), N, H, W, nearest_channel, relu,
-                                                        _lib.stream_of(a)), "slr_upsample2x_concat")
+        _call("slr_upsample2x_concat", a.device, a, Ca, b, Cb, out, N, H, W, nearest_channel, relu)
         return out
 
     def up(x):
@@ -1104,8 +1057,8 @@ def load_motion_state_dict(net, sd, prefix):
         used.update(k for k in (key + ".weight", key + ".weight_orig", key + ".weight_u", key + ".weight_v") if k in sub)
         if tuple(w.shape) != tuple(mod.weight.shape):
             raise ValueError(f"{prefix}{key}: weight {tuple(w.shape)}, the network expects {tuple(mod.weight.shape)}")
-        mod.weight.data.copy_(w)
-        mod.bias.data.copy_(_take(sub, used, key + ".bias"))
+        mod.weight.copy_(w)
+        mod.bias.copy_(_take(sub, used, key + ".bias"))
 
     def bn(mod, key):
         for name in ("running_mean", "running_var", "weight", "bias"):
@@ -1125,10 +1078,10 @@ def load_motion_state_dict(net, sd, prefix):
         for s in list(_MOTION_ENC_NORM.values()) + list(_MOTION_DEC_NORM.values()):
             sp = getattr(net, f"spade_layer{s}")
             key = f"spade_layer{s}"
-            sp.mlp_shared.weight.data.copy_(_take(sub, used, key + ".mlp_shared.0.weight"))
-            sp.mlp_shared.bias.data.copy_(_take(sub, used, key + ".mlp_shared.0.bias"))
-            sp.mlp_gb.weight.data.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.weight"), _take(sub, used, key + ".mlp_beta.weight")]))
-            sp.mlp_gb.bias.data.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.bias"), _take(sub, used, key + ".mlp_beta.bias")]))
+            sp.mlp_shared.weight.copy_(_take(sub, used, key + ".mlp_shared.0.weight"))
+            sp.mlp_shared.bias.copy_(_take(sub, used, key + ".mlp_shared.0.bias"))
+            sp.mlp_gb.weight.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.weight"), _take(sub, used, key + ".mlp_beta.weight")]))
+            sp.mlp_gb.bias.copy_(torch.cat([_take(sub, used, key + ".mlp_gamma.bias"), _take(sub, used, key + ".mlp_beta.bias")]))
     left = sorted(set(sub) - used)
     if left:
         raise KeyError(f"motion U-Net: {len(left)} key(s) under {prefix!r} not consumed (another norm / architecture?): {left[:6]}")

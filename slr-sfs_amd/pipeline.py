@@ -109,13 +109,6 @@ def _encode(encoder, image, shard, policy="split", owner=None, what="encoder"):
 
 
 CONV_POLICIES = ("auto", "split", "fp32", "fp32-winograd")
-_RUNG_SCALE = (64.0, 1.0)
-
-
-def _rung_context(rung):
-    """Arithmetic of the decoder convolutions by rung of the ladder: 0 split-f16 at activation scale 2^6 (exact for
-    |x| < 1023), 1 split-f16 at scale 1 (|x| < 65472), 2 the fp32 matrix instructions (nets.fp32_kernels: no limit)."""
-    return nets.fp32_kernels(winograd=False) if rung >= 2 else nets.activation_scale(_RUNG_SCALE[rung])
 
 
 def _render(owner, clip, frames, batch, overlap, decode, policy, on_frame, one_by_one=False):
@@ -168,9 +161,9 @@ def _render(owner, clip, frames, batch, overlap, decode, policy, on_frame, one_b
         for i0, gen, afl in groups(frames):
             pos = list(range(i0, i0 + gen.shape[0]))
             while True:
-                with _rung_context(rung):
+                with nets.rung_context(rung):
                     outs = decode_batch(gen, afl)
-                if rung >= 2 or nets.saturation_count(dev) == 0:
+                if rung >= nets.RUNG_FP32 or nets.saturation_count(dev) == 0:
                     break
                 rung += 1
                 owner._conv_rung = rung
@@ -181,14 +174,14 @@ def _render(owner, clip, frames, batch, overlap, decode, policy, on_frame, one_b
     todo = list(range(len(frames)))                       # positions still to render
     while todo:
         sub = [frames[p_] for p_ in todo]
-        if rung >= 2:
-            with _rung_context(rung):
+        if rung >= nets.RUNG_FP32:
+            with nets.rung_context(rung):
                 for i0, gen, afl in groups(sub):
                     store([todo[i0 + k] for k in range(gen.shape[0])], decode_batch(gen, afl))
             return
         log = nets.SaturationLog(dev, len(sub))
         spans = []
-        with _rung_context(rung):
+        with nets.rung_context(rung):
             for i0, gen, afl in groups(sub):
                 pos = [todo[i0 + k] for k in range(gen.shape[0])]
                 store(pos, decode_batch(gen, afl))

@@ -288,3 +288,20 @@ def test_failed_call_drops_cached_workspaces():
         _lib.check(-1, "test")                           # an argument error launched nothing: the cache stays
     assert _lib._ws_cache
     _lib.clear_workspaces()
+
+
+def test_bn_scale_shift_follows_in_place_updates():
+    """AffineBN.scale_shift() is cached per (data_ptr, _version, device) of the statistics: an in-place update after a first call
+    (what nn.Module.load_state_dict does) is seen by the next call."""
+    from slr_sfs_amd import nets
+    bn = nets.AffineBN(4)
+    scale, shift = bn.scale_shift()
+    assert scale is bn.scale_shift()[0]                    # cached while nothing changes
+    with torch.no_grad():
+        bn.stored_var.copy_(torch.tensor([9.0, 64.0, 225.0, 0.25]) - bn.eps)
+    scale, shift = bn.scale_shift()
+    assert torch.allclose(scale, torch.tensor([1 / 3.0, 1 / 8.0, 1 / 15.0, 2.0]))
+    sd = {"stored_mean": torch.tensor([1.0, 2.0, 3.0, 4.0]), "stored_var": torch.full((4,), 4.0 - bn.eps)}
+    bn.load_state_dict(sd)
+    scale, shift = bn.scale_shift()
+    assert torch.allclose(scale, torch.full((4,), 0.5)) and torch.allclose(shift, torch.tensor([0.5, 1.0, 1.5, 2.0]))
