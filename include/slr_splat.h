@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 11
+#define SLR_ABI_VERSION 12
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -506,6 +506,36 @@ int slr_resize_segmap(const float *in, float *out, int N, int C, int H, int W, i
  * relu = 1: ReLU of the inputs (up(relu(cat)), architectures.py:463-489 and e8 at :710); 2: ReLU of the output (:715-741); 0: none. */
 int slr_upsample2x_concat(const float *a, int Ca, const float *b, int Cb, float *out, int N, int H, int W, int nearest_channel, int relu,
                           void *stream);
+
+/* ------------------------------------------------------------------ clip-evaluation metrics (ABI 12; csrc/metrics.hip)
+ * The reference scores clips with evaluation/animation/metrics.py (psnr, ssim_metric, perceptual_sim) on models/losses/ssim.py and
+ * models/networks/pretrained_networks.py (PNet "vgg").  Images are float [N,C,H,W] in [0,1] (u8 = 0) or uint8 [N,H,W,C] frames as
+ * decoders give them (u8 = 1; the value is v / 255.0f, i.e. ToTensor).  Reductions are deterministic (fixed order, no atomics) and a
+ * result depends on its own image only.  The VGG16 convolutions run on slr_conv3x3_forward with SLR_CONV_F32 (channel-blocked
+ * features, the ReLU between them as the prologue with scale 1 / shift 0). */
+
+/* models/losses/ssim.py:_ssim (window_size odd, 1 .. 15, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2) and the squared error of
+ * evaluation/animation/metrics.py:psnr in ONE pass: out [N,2] = per image (ssim, mse).  mask [N,1,H,W] or NULL: with a mask
+ * ssim = sum(mask * mean_c(ssim_map)) / max(sum(mask), 1) (ssim.py:61-67) and mse = sum(mask * err^2) / (3 max(sum(mask), 1))
+ * (metrics.py:12-17); without, both are means over C, H, W (ssim.py:76, metrics.py:20).  ws: slr_ssim_ws_bytes(N, H, W) bytes,
+ * 8-byte aligned (per-tile partial sums). */
+size_t slr_ssim_ws_bytes(int N, int H, int W);
+int slr_ssim_mse(const void *img1, const void *img2, int u8, const float *mask, float *out, int N, int C, int H, int W,
+                 int window_size, void *ws, size_t ws_bytes, void *stream);
+
+/* The input of PNet's VGG16 (metrics.py:29 + pretrained_networks.py:45-46, 73-74): out [N,3,H,W] NCHW = ((x * 2 - 1) - shift) / scale
+ * with from01 = 1 (images in [0,1]; uint8 frames need it), (x - shift) / scale with from01 = 0 (PNet.forward's own [-1,1] input). */
+int slr_vgg_prep(const void *img, int u8, int from01, float *out, int N, int H, int W, void *stream);
+
+/* nn.ReLU + nn.MaxPool2d(2, stride 2) of torchvision's vgg16.features (floor mode: 45 x 80 -> 22 x 40):
+ * in [N,C,H,W] -> out [N,C,H/2,W/2], both channel-blocked [N,C/8,.,.,8], C % 8 == 0, 16-byte aligned. */
+int slr_relu_maxpool2x2_b8(const float *in, float *out, int N, int C, int H, int W, void *stream);
+
+/* 1 - cos_sim(relu(f0), relu(f1)) of pretrained_networks.py:11-31 and :82 (normalize_tensor eps 1e-10; mean over H, W):
+ * f0, f1 [N,C,H,W] channel-blocked (C % 8 == 0), out [N].  ws: slr_feature_cos_ws_bytes(N, H, W) bytes, 8-byte aligned. */
+size_t slr_feature_cos_ws_bytes(int N, int H, int W);
+int slr_feature_cos_distance(const float *f0, const float *f1, float *out, int N, int C, int H, int W, void *ws, size_t ws_bytes,
+                             void *stream);
 
 #ifdef __cplusplus
 }

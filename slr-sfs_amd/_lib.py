@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 11
+ABI_VERSION = 12
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # every symbol include/slr_splat.h declares
@@ -29,6 +29,7 @@ SYMBOLS = (
     "slr_avgpool3x3s2", "slr_upsample_bilinear2x", "slr_conv1x1_small",
     "slr_conv4x4s2_weight_bytes", "slr_conv4x4s2_f32_weights", "slr_conv4x4s2_forward", "slr_instnorm_spade", "slr_resize_segmap",
     "slr_upsample2x_concat",
+    "slr_ssim_ws_bytes", "slr_ssim_mse", "slr_vgg_prep", "slr_relu_maxpool2x2_b8", "slr_feature_cos_ws_bytes", "slr_feature_cos_distance",
 )
 
 _lib = None
@@ -86,6 +87,10 @@ def lib():
         L.slr_conv_up_ws_bytes.argtypes = [i, i, i, i]
         L.slr_conv4x4s2_weight_bytes.restype = sz
         L.slr_conv4x4s2_weight_bytes.argtypes = [i, i]
+        L.slr_ssim_ws_bytes.restype = sz
+        L.slr_ssim_ws_bytes.argtypes = [i, i, i]
+        L.slr_feature_cos_ws_bytes.restype = sz
+        L.slr_feature_cos_ws_bytes.argtypes = [i, i, i]
         sig = {
             "slr_euler_integrate": [fp, i, i, i, f, fp, fp, vp],
             "slr_euler_integrate_all": [fp, i, i, i, f, fp, fp, vp],
@@ -134,6 +139,10 @@ def lib():
             "slr_instnorm_spade": [fp, fp, fp, i, i, i, i, f, vp],
             "slr_resize_segmap": [fp, fp, i, i, i, i, i, i, vp],
             "slr_upsample2x_concat": [fp, i, fp, i, fp, i, i, i, i, i, vp],
+            "slr_ssim_mse": [vp, vp, i, fp, fp, i, i, i, i, i, vp, sz, vp],
+            "slr_vgg_prep": [vp, i, i, fp, i, i, i, vp],
+            "slr_relu_maxpool2x2_b8": [fp, fp, i, i, i, i, vp],
+            "slr_feature_cos_distance": [fp, fp, fp, i, i, i, i, vp, sz, vp],
         }
         for name, argtypes in sig.items():
             fn = getattr(L, name)

@@ -60,13 +60,14 @@ def predict_scene_motion(model, image, flow, W, points=None):
 
 
 def animate_scene(model, image_path, flow_path, out_dir, name, H, W, N, speed, align=None, rank=0, world=1, group=None,
-                  video=True, half_size=False, predict_motion=False, hint_points=None, write_motion=False):
+                  video=True, half_size=False, predict_motion=False, hint_points=None, write_motion=False, score=None):
     """One scene -> out_dir/name/PredImg/%06d.png (2-layer model: + FluidImg/, CompositeFluidAlpha/, BGImg.png;
     test_v1_4eval_rawsize.py:240-284), written by rank 0, at the raw size of the image (the *_rawsize scripts) or at half
     of it (half_size: test_baseline_4eval.py / test_v1_4eval.py:160-161).  predict_motion: the motion is predicted from the image by
     the model's motion regressor, with the mask / hints derived from the scene's flow (predict_scene_motion; ``hint_points`` [(y, x)]
     pins the hints; the hint branch forces speed 1), every rank predicting it; write_motion: rank 0 also writes the field used as
-    out_dir/name/Motion.flo.  Returns (seconds of device work, frame dir)."""
+    out_dir/name/Motion.flo; score: rank 0 calls score(frames) with the uint8 [n,h,w,3] device frames it writes.
+    Returns (seconds of device work, frame dir)."""
     v1 = isinstance(model, pipeline.SLRv1Animator)
     dev = next(model.parameters()).device
     image, (raw_w, raw_h) = io.load_image(image_path, H, W)
@@ -100,7 +101,10 @@ def animate_scene(model, image_path, flow_path, out_dir, name, H, W, N, speed, a
         if write_motion:
             os.makedirs(scene, exist_ok=True)
             io.write_flo(os.path.join(scene, "Motion.flo"), motion[0].permute(1, 2, 0).cpu().numpy())
-        io.save_frames(io.frames_to_uint8(clips["PredImg"], (raw_h, raw_w)), scene)
+        pred_u8 = io.frames_to_uint8(clips["PredImg"], (raw_h, raw_w))
+        io.save_frames(pred_u8, scene)
+        if score is not None:
+            score(pred_u8)
         if v1:
             io.save_frames(io.frames_to_uint8(clips["FluidImg"], (raw_h, raw_w)), scene, key="FluidImg")
             io.save_frames(io.alpha_to_uint8(clips["CompositeFluidAlpha"], (raw_h, raw_w)), scene, key="CompositeFluidAlpha")

@@ -51,13 +51,35 @@ def main():
                     help="the 5 hint pixels 'y,x;y,x;...' at the flow's resolution (default: a deterministic k-means of the moving region, "
                          "whose positions are not those of the reference's sklearn KMeans)")
     ap.add_argument("--write-motion", action="store_true", help="also write the motion field used as OUTDIR/NAME/Motion.flo")
+    ap.add_argument("--gt-frames", default=None,
+                    help="ground truth of the clip (a directory of %%06d.png / .jpg frames or a uint8 [n,h,w,3] .npy): score the frames on "
+                         "the device (PSNR, SSIM; tools/evaluate.py's metric.json for this one scene), from the uint8 frames written")
+    ap.add_argument("--metrics-json", default=None, help="where --gt-frames writes its JSON (default OUTDIR/../metric.json)")
+    ap.add_argument("--perceptual-weights", default=None, help="with --gt-frames: a torchvision VGG16 state dict, adds Perceptual")
     a = ap.parse_args()
     rank, world, dev = init_ranks()
     model = runner.load_model(a.ckpt, a.v1, dev, motion_ckpt=a.motion_ckpt)
     points = None if a.hint_points is None else [tuple(int(v) for v in p.split(",")) for p in a.hint_points.split(";")]
+    score = None
+    if a.gt_frames and rank == 0:
+        def score(frames):
+            import json
+            from slr_sfs_amd import evaluation, metrics
+            src = ("npy", a.gt_frames) if a.gt_frames.endswith(".npy") else ("frames", a.gt_frames)
+            gt = evaluation.load_gt(src, frames.shape[0])
+            if gt is None or gt.shape[0] < frames.shape[0]:
+                raise ValueError(f"--gt-frames {a.gt_frames}: fewer than {frames.shape[0]} frames")
+            gt = torch.from_numpy(evaluation.resize_like_reference(gt, tuple(frames.shape[1:3]))).to(frames.device)
+            vgg = metrics.PerceptualVGG16.from_file(a.perceptual_weights, frames.device) if a.perceptual_weights else None
+            per = {k: v.cpu().tolist() for k, v in metrics.evaluate_clip(frames.contiguous(), gt, perceptual=vgg).items()}
+            res = evaluation.aggregate({a.name: per}, evaluation.KEYS if vgg is not None else ("PSNR", "SSIM"))
+            path = a.metrics_json or os.path.join(a.outdir, "..", "metric.json")
+            with open(path, "w") as f:
+                json.dump(res, f)
+            print(f"metrics of {a.name}: PSNR {res['TotalPSNR']:.4f} SSIM {res['TotalSSIM']:.5f} -> {path}")
     dt, out = runner.animate_scene(model, a.image, a.flow, a.outdir, a.name, a.H or a.W, a.W, a.N, a.speed, a.align, rank, world,
                                    half_size=a.half_size, predict_motion=bool(a.motion_ckpt or a.predict_motion), hint_points=points,
-                                   write_motion=a.write_motion)
+                                   write_motion=a.write_motion, score=score)
     if rank == 0:
         print(f"{a.N} frames at {a.H or a.W}x{a.W} on {world} GPU(s) in {dt:.2f} s ({a.N / dt:.1f} frames/s) -> {out}")
     if world > 1:
