@@ -10,27 +10,79 @@ LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libs
 ABI_VERSION = 12
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
-# every symbol include/slr_splat.h declares
-SYMBOLS = (
-    "slr_abi_version", "slr_last_error", "slr_splat_time_next",
-    "slr_euler_integrate", "slr_euler_integrate_all", "slr_euler_backward", "slr_euler_integrate_batch", "slr_euler_backward_batch",
-    "slr_splat_workspace_bytes", "slr_splat_workspace_init", "slr_splat_bin", "slr_splat_bin_pair", "slr_splat_set_scan_max_tiles",
-    "slr_splat_set_front_end",
-    "slr_splat_set_scan_shape",
-    "slr_softsplat_forward", "slr_softsplat_mode_forward", "slr_splat_normalize",
-    "slr_synth_group", "slr_global_max",
-    "slr_clip_plan_bytes", "slr_clip_plan_totals", "slr_clip_plan_build", "slr_synth_group_clip",
-    "slr_synth_group_clip_batch", "slr_synth_two_groups_clip_batch", "slr_pack_planes4",
-    "slr_softsplat_backward", "slr_softsplat_backward_ws_bytes", "slr_softsplat_backward_ws", "slr_maxsplat_forward", "slr_max_warp_norm",
-    "slr_bn_relu_mask", "slr_pconv_epilogue", "slr_conv_saturation_count", "slr_conv_saturation_record",
-    "slr_conv3x3_weight_bytes", "slr_conv3x3_split_weights", "slr_conv3x3_f32_weights", "slr_conv3x3_wino_weight_bytes", "slr_conv3x3_wino_weights", "slr_conv3x3_forward", "slr_pconv3x3_forward",
-    "slr_conv3x3_forward_skip", "slr_pconv3x3_forward_skip", "slr_conv_pool_ws_bytes", "slr_conv_up_ws_bytes", "slr_conv3x3_forward_skipout", "slr_pconv3x3_forward_skipout",
-    "slr_conv1x1_weight_bytes", "slr_conv1x1_split_weights", "slr_conv1x1_f32_weights", "slr_conv1x1_forward",
-    "slr_avgpool3x3s2", "slr_upsample_bilinear2x", "slr_conv1x1_small",
-    "slr_conv4x4s2_weight_bytes", "slr_conv4x4s2_f32_weights", "slr_conv4x4s2_forward", "slr_instnorm_spade", "slr_resize_segmap",
-    "slr_upsample2x_concat",
-    "slr_ssim_ws_bytes", "slr_ssim_mse", "slr_vgg_prep", "slr_relu_maxpool2x2_b8", "slr_feature_cos_ws_bytes", "slr_feature_cos_distance",
-)
+# The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
+_vp, _fp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+SIGNATURES = {
+    "slr_abi_version": (_i, []),
+    "slr_last_error": (ctypes.c_char_p, []),
+    "slr_splat_time_next": (None, [_vp, _vp]),
+    "slr_euler_integrate": (_i, [_fp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_euler_integrate_all": (_i, [_fp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_euler_backward": (_i, [_fp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_euler_integrate_batch": (_i, [_fp, _vp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_euler_backward_batch": (_i, [_fp, _vp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_splat_workspace_bytes": (_sz, [_i, _i, _i]),
+    "slr_splat_workspace_init": (_i, [_vp, _sz, _i, _i, _i, _vp]),
+    "slr_splat_bin": (_i, [_fp, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_splat_bin_pair": (_i, [_fp, _fp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "slr_splat_set_scan_max_tiles": (_i, [_i]),
+    "slr_splat_set_front_end": (_i, [_i]),
+    "slr_splat_set_scan_shape": (None, [_i, _i, _i, _i]),
+    "slr_softsplat_forward": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "slr_softsplat_mode_forward": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "slr_splat_normalize": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _vp]),
+    "slr_synth_group": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _f, _fp, _fp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "slr_clip_plan_bytes": (_sz, [_i, _i, _i]),
+    "slr_clip_plan_totals": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    "slr_clip_plan_build": (_i, [_fp, _vp, _fp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_pack_planes4": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
+    "slr_synth_group_clip_batch": (_i, [_fp, _fp, _fp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _i, _vp, _i, _vp, _vp]),
+    "slr_synth_two_groups_clip_batch": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _i, _vp, _i, _vp, _vp]),
+    "slr_synth_group_clip": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _f, _fp, _fp, _i, _i, _i, _f, _vp, _sz, _i, _i, _i, _vp]),
+    "slr_global_max": (_i, [_fp, _sz, _fp, _fp, _vp]),
+    "slr_softsplat_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "slr_softsplat_backward_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "slr_softsplat_backward_ws": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_maxsplat_forward": (_i, [_fp, _fp, _fp, _f, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "slr_max_warp_norm": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "slr_bn_relu_mask": (_i, [_fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _vp]),
+    "slr_pconv_epilogue": (_i, [_fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _f, _i, _i, _i, _i, _vp]),
+    "slr_conv_saturation_count": (_i, [ctypes.POINTER(ctypes.c_ulonglong), _i, _vp]),
+    "slr_conv_saturation_record": (_i, [_vp, _vp]),
+    "slr_conv3x3_weight_bytes": (_sz, [_i, _i]),
+    "slr_conv3x3_split_weights": (_i, [_fp, _vp, _i, _i, _f, _vp]),
+    "slr_conv3x3_f32_weights": (_i, [_fp, _vp, _i, _i, _vp]),
+    "slr_conv3x3_wino_weight_bytes": (_sz, [_i, _i]),
+    "slr_conv3x3_wino_weights": (_i, [_fp, _vp, _i, _i, _vp]),
+    "slr_conv3x3_forward": (_i, [_fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _fp, _fp, _i, _vp]),
+    "slr_pconv3x3_forward": (_i, [_fp, _fp, _fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "slr_conv_pool_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "slr_conv_up_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "slr_conv3x3_forward_skip": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _fp, _fp, _fp, _vp, _fp, _i, _f, _vp, _sz, _i, _vp]),
+    "slr_pconv3x3_forward_skip": (_i, [_fp, _fp, _fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp, _i, _f, _vp, _sz, _i, _vp]),
+    "slr_conv3x3_forward_skipout": (_i, [_fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _fp, _fp, _fp, _fp, _fp, _i, _vp]),
+    "slr_pconv3x3_forward_skipout": (_i, [_fp, _fp, _fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _i, _vp]),
+    "slr_conv1x1_weight_bytes": (_sz, [_i, _i]),
+    "slr_conv1x1_split_weights": (_i, [_fp, _vp, _i, _i, _f, _vp]),
+    "slr_conv1x1_f32_weights": (_i, [_fp, _vp, _i, _i, _vp]),
+    "slr_conv1x1_forward": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "slr_avgpool3x3s2": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_upsample_bilinear2x": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_conv1x1_small": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "slr_conv4x4s2_weight_bytes": (_sz, [_i, _i]),
+    "slr_conv4x4s2_f32_weights": (_i, [_fp, _vp, _i, _i, _vp]),
+    "slr_conv4x4s2_forward": (_i, [_fp, _vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "slr_instnorm_spade": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _f, _vp]),
+    "slr_resize_segmap": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "slr_upsample2x_concat": (_i, [_fp, _i, _fp, _i, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_ssim_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_ssim_mse": (_i, [_vp, _vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_vgg_prep": (_i, [_vp, _i, _i, _fp, _i, _i, _i, _vp]),
+    "slr_relu_maxpool2x2_b8": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
+    "slr_feature_cos_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_feature_cos_distance": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
+}
+SYMBOLS = tuple(SIGNATURES)
 
 _lib = None
 _lock = threading.Lock()
@@ -58,96 +110,9 @@ def lib():
                 f"`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C slr-sfs_amd/csrc`). "
                 f"There is no CPU/PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        vp, fp, i, f, sz = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-        L.slr_abi_version.restype = i
-        L.slr_last_error.restype = ctypes.c_char_p
-        L.slr_splat_time_next.restype = None
-        L.slr_splat_time_next.argtypes = [vp, vp]
-        L.slr_splat_set_scan_max_tiles.restype = i
-        L.slr_splat_set_scan_max_tiles.argtypes = [i]
-        L.slr_splat_set_front_end.restype = i
-        L.slr_splat_set_front_end.argtypes = [i]
-        L.slr_splat_set_scan_shape.restype = None
-        L.slr_splat_set_scan_shape.argtypes = [i, i, i, i]
-        L.slr_splat_workspace_bytes.restype = sz
-        L.slr_splat_workspace_bytes.argtypes = [i, i, i]
-        L.slr_softsplat_backward_ws_bytes.restype = sz
-        L.slr_softsplat_backward_ws_bytes.argtypes = [i, i, i, i]
-        L.slr_clip_plan_bytes.restype = sz
-        L.slr_clip_plan_bytes.argtypes = [i, i, i]
-        L.slr_conv3x3_weight_bytes.restype = sz
-        L.slr_conv3x3_weight_bytes.argtypes = [i, i]
-        L.slr_conv3x3_wino_weight_bytes.restype = sz
-        L.slr_conv3x3_wino_weight_bytes.argtypes = [i, i]
-        L.slr_conv1x1_weight_bytes.restype = sz
-        L.slr_conv1x1_weight_bytes.argtypes = [i, i]
-        L.slr_conv_pool_ws_bytes.restype = sz
-        L.slr_conv_pool_ws_bytes.argtypes = [i, i, i, i]
-        L.slr_conv_up_ws_bytes.restype = sz
-        L.slr_conv_up_ws_bytes.argtypes = [i, i, i, i]
-        L.slr_conv4x4s2_weight_bytes.restype = sz
-        L.slr_conv4x4s2_weight_bytes.argtypes = [i, i]
-        L.slr_ssim_ws_bytes.restype = sz
-        L.slr_ssim_ws_bytes.argtypes = [i, i, i]
-        L.slr_feature_cos_ws_bytes.restype = sz
-        L.slr_feature_cos_ws_bytes.argtypes = [i, i, i]
-        sig = {
-            "slr_euler_integrate": [fp, i, i, i, f, fp, fp, vp],
-            "slr_euler_integrate_all": [fp, i, i, i, f, fp, fp, vp],
-            "slr_euler_backward": [fp, i, i, i, f, fp, fp, vp],
-            "slr_euler_integrate_batch": [fp, vp, i, i, i, f, fp, fp, vp],
-            "slr_euler_backward_batch": [fp, vp, i, i, i, f, fp, fp, vp],
-            "slr_splat_workspace_init": [vp, sz, i, i, i, vp],
-            "slr_splat_bin": [fp, i, i, i, vp, sz, vp],
-            "slr_splat_bin_pair": [fp, fp, i, i, i, vp, vp, sz, vp],
-            "slr_softsplat_forward": [fp, fp, fp, i, i, i, i, vp, sz, i, vp],
-            "slr_softsplat_mode_forward": [fp, fp, fp, fp, i, i, i, i, i, vp, sz, i, vp],
-            "slr_splat_normalize": [fp, fp, i, i, i, i, i, f, vp],
-            "slr_synth_group": [fp, fp, fp, i, fp, fp, f, fp, fp, i, i, i, f, vp, vp, sz, vp],
-            "slr_global_max": [fp, sz, fp, fp, vp],
-            "slr_clip_plan_totals": [i, i, i, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)],
-            "slr_clip_plan_build": [fp, vp, fp, vp, i, i, i, vp, sz, vp],
-            "slr_synth_group_clip": [fp, fp, fp, i, fp, fp, f, fp, fp, i, i, i, f, vp, sz, i, i, i, vp],
-            "slr_synth_group_clip_batch": [fp, fp, fp, i, vp, vp, vp, vp, vp, i, i, i, f, vp, sz, i, vp, i, vp, vp],
-            "slr_pack_planes4": [fp, fp, i, i, i, i, vp],
-            "slr_synth_two_groups_clip_batch": [fp, fp, fp, i, fp, fp, i, vp, vp, vp, vp, vp, i, i, i, f, vp, sz, i, vp, i, vp, vp],
-            "slr_softsplat_backward": [fp, fp, fp, fp, fp, i, i, i, i, vp],
-            "slr_softsplat_backward_ws": [fp, fp, fp, fp, fp, i, i, i, i, vp, sz, vp],
-            "slr_maxsplat_forward": [fp, fp, fp, f, i, i, i, i, vp, sz, i, vp],
-            "slr_max_warp_norm": [fp, fp, fp, fp, i, i, i, i, vp, sz, i, vp],
-            "slr_bn_relu_mask": [fp, fp, fp, fp, i, fp, i, i, i, i, vp],
-            "slr_pconv_epilogue": [fp, fp, fp, f, fp, fp, fp, fp, fp, f, i, i, i, i, vp],
-            "slr_conv_saturation_count": [ctypes.POINTER(ctypes.c_ulonglong), i, vp],
-            "slr_conv_saturation_record": [vp, vp],
-            "slr_conv3x3_split_weights": [fp, vp, i, i, f, vp],
-            "slr_conv1x1_split_weights": [fp, vp, i, i, f, vp],
-            "slr_conv3x3_f32_weights": [fp, vp, i, i, vp],
-            "slr_conv3x3_wino_weights": [fp, vp, i, i, vp],
-            "slr_conv1x1_f32_weights": [fp, vp, i, i, vp],
-            "slr_conv1x1_forward": [fp, vp, fp, fp, i, i, i, i, i, f, f, i, vp],
-            "slr_conv3x3_forward": [fp, vp, fp, fp, fp, i, i, i, i, i, f, f, fp, fp, i, vp],
-            "slr_pconv3x3_forward": [fp, fp, fp, fp, vp, f, f, fp, fp, fp, fp, fp, fp, i, i, i, i, i, i, vp],
-            "slr_conv3x3_forward_skip": [fp, vp, fp, fp, i, i, i, i, i, f, f, fp, fp, fp, vp, fp, i, f, vp, sz, i, vp],
-            "slr_pconv3x3_forward_skip": [fp, fp, fp, fp, vp, f, f, fp, fp, fp, i, i, i, i, i, fp, vp, i, f, vp, sz, i, vp],
-            "slr_conv3x3_forward_skipout": [fp, vp, fp, fp, fp, i, i, i, i, i, f, f, fp, fp, fp, fp, fp, i, vp],
-            "slr_pconv3x3_forward_skipout": [fp, fp, fp, fp, vp, f, f, fp, fp, fp, fp, fp, fp, i, i, i, i, i, fp, fp, i, vp],
-            "slr_avgpool3x3s2": [fp, fp, i, i, i, i, i, vp],
-            "slr_upsample_bilinear2x": [fp, fp, i, i, i, i, i, vp],
-            "slr_conv1x1_small": [fp, fp, fp, fp, i, i, i, i, i, i, vp],
-            "slr_conv4x4s2_f32_weights": [fp, vp, i, i, vp],
-            "slr_conv4x4s2_forward": [fp, vp, fp, fp, fp, fp, i, i, i, i, i, i, f, vp],
-            "slr_instnorm_spade": [fp, fp, fp, i, i, i, i, f, vp],
-            "slr_resize_segmap": [fp, fp, i, i, i, i, i, i, vp],
-            "slr_upsample2x_concat": [fp, i, fp, i, fp, i, i, i, i, i, vp],
-            "slr_ssim_mse": [vp, vp, i, fp, fp, i, i, i, i, i, vp, sz, vp],
-            "slr_vgg_prep": [vp, i, i, fp, i, i, i, vp],
-            "slr_relu_maxpool2x2_b8": [fp, fp, i, i, i, i, vp],
-            "slr_feature_cos_distance": [fp, fp, fp, i, i, i, i, vp, sz, vp],
-        }
-        for name, argtypes in sig.items():
+        for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(L, name)
-            fn.argtypes = argtypes
-            fn.restype = i
+            fn.restype, fn.argtypes = restype, argtypes
         if L.slr_abi_version() != ABI_VERSION:
             raise RuntimeError(f"slr_sfs_amd: {LIB_PATH} has ABI {L.slr_abi_version()}, expected {ABI_VERSION}")
         _lib = L
@@ -166,6 +131,14 @@ def check(rc, what):
 
 def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def call(name, device, *args):
+    """Entry point ``name`` of the library, looked up at every call, with ``args`` (tensors as their device pointers) and torch's
+    current stream on ``device``, run with ``device`` current; raises naming the entry point if it fails."""
+    args = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]   # (isinstance: ~1.5 us less per call than torch.is_tensor)
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), name)
 
 
 def stream_of(t):
@@ -218,8 +191,7 @@ def workspace(t, role, N, C, H, W, nbytes=None):
             _ws_cache.popitem(last=False)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
         # a splat workspace starts zeroed; the kernels leave its counters zero again, so the calls may say WS_CLEAN (no zero kernel)
-        with torch.cuda.device(t.device):
-            check(lib().slr_splat_workspace_init(ptr(ws), ws.numel(), N, H, W, ctypes.c_void_p(stream.cuda_stream)), "slr_splat_workspace_init")
+        call("slr_splat_workspace_init", t.device, ws, ws.numel(), N, H, W)
         _ws_cache[key] = ws
     else:
         _ws_cache.move_to_end(key)

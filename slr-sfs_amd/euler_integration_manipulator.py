@@ -8,7 +8,7 @@ loop of ~15 torch kernels per step, euler_integration_manipulator.py:36-55).
 import torch
 import torch.nn as nn
 
-from ._lib import check, lib, ptr, require_device, stream_of
+from ._lib import call, require_device
 
 
 def _steps(destination_frame):
@@ -48,9 +48,7 @@ def _integrate(motion, n):
     _, _, height, width = motion.shape
     disp = torch.empty_like(motion)
     vis = motion.new_empty(1, 1, height, width)
-    with torch.cuda.device(motion.device):
-        check(lib().slr_euler_integrate(ptr(motion), height, width, n, 1.0, ptr(disp), ptr(vis),
-                                        stream_of(motion)), "slr_euler_integrate")
+    call("slr_euler_integrate", motion.device, motion, height, width, n, 1.0, disp, vis)
     return disp, vis
 
 
@@ -74,9 +72,7 @@ class _EulerIntegrate(torch.autograd.Function):
         require_device(grad_disp)
         _, _, height, width = motion.shape
         grad_motion = torch.empty_like(motion)
-        with torch.cuda.device(motion.device):
-            check(lib().slr_euler_backward(ptr(motion), height, width, ctx.n, 1.0, ptr(grad_disp), ptr(grad_motion),
-                                           stream_of(motion)), "slr_euler_backward")
+        call("slr_euler_backward", motion.device, motion, height, width, ctx.n, 1.0, grad_disp, grad_motion)
         return grad_motion, None
 
 
@@ -92,9 +88,7 @@ def euler_integration_all(motion, nmax, sign=1.0, want_visible=True):
     _, _, H, W = motion.shape
     disp = motion.new_empty(nmax + 1, 2, H, W)
     vis = motion.new_empty(nmax + 1, 1, H, W) if want_visible else None
-    with torch.cuda.device(motion.device):
-        check(lib().slr_euler_integrate_all(ptr(motion), H, W, int(nmax), float(sign), ptr(disp), ptr(vis),
-                                            stream_of(motion)), "slr_euler_integrate_all")
+    call("slr_euler_integrate_all", motion.device, motion, H, W, int(nmax), float(sign), disp, vis)
     return disp, vis
 
 
@@ -113,9 +107,7 @@ def _integrate_batch(motion, steps):
     b, _, height, width = motion.shape
     disp = torch.empty_like(motion)
     vis = motion.new_empty(b, 1, height, width)
-    with torch.cuda.device(motion.device):
-        check(lib().slr_euler_integrate_batch(ptr(motion), ptr(steps), b, height, width, 1.0, ptr(disp), ptr(vis),
-                                              stream_of(motion)), "slr_euler_integrate_batch")
+    call("slr_euler_integrate_batch", motion.device, motion, steps, b, height, width, 1.0, disp, vis)
     return disp, vis
 
 
@@ -136,9 +128,7 @@ class _EulerIntegrateBatch(torch.autograd.Function):
         require_device(grad_disp)
         b, _, height, width = motion.shape
         grad_motion = torch.empty_like(motion)
-        with torch.cuda.device(motion.device):
-            check(lib().slr_euler_backward_batch(ptr(motion), ptr(steps), b, height, width, 1.0, ptr(grad_disp),
-                                                 ptr(grad_motion), stream_of(motion)), "slr_euler_backward_batch")
+        call("slr_euler_backward_batch", motion.device, motion, steps, b, height, width, 1.0, grad_disp, grad_motion)
         return grad_motion, None
 
 

@@ -52,7 +52,7 @@ def ssim_mse(img1, img2, window_size=11, mask=None):
         _lib.require_device(mask)
     out = torch.empty(N, 2, device=img1.device, dtype=torch.float32)
     ws = torch.empty(_lib.lib().slr_ssim_ws_bytes(N, H, W), dtype=torch.uint8, device=img1.device)
-    nets._call("slr_ssim_mse", img1.device, img1, img2, u8, mask, out, N, C, H, W, int(window_size), ws, ws.numel())
+    _lib.call("slr_ssim_mse", img1.device, img1, img2, u8, mask, out, N, C, H, W, int(window_size), ws, ws.numel())
     return out
 
 
@@ -92,7 +92,7 @@ def relu_maxpool2x2(x):
     """nn.ReLU + nn.MaxPool2d(2, 2) of channel-blocked [N,C,H,W] activations (floor mode) -> channel-blocked [N,C,H//2,W//2]."""
     N, C, H, W = x.shape
     out = torch.empty(N, C, H // 2, W // 2, device=x.device, dtype=x.dtype)
-    nets._call("slr_relu_maxpool2x2_b8", x.device, x, out, N, C, H, W)
+    _lib.call("slr_relu_maxpool2x2_b8", x.device, x, out, N, C, H, W)
     return out
 
 
@@ -101,7 +101,7 @@ def feature_distance(f0, f1):
     N, C, H, W = f0.shape
     out = torch.empty(N, device=f0.device, dtype=torch.float32)
     ws = torch.empty(_lib.lib().slr_feature_cos_ws_bytes(N, H, W), dtype=torch.uint8, device=f0.device)
-    nets._call("slr_feature_cos_distance", f0.device, f0, f1, out, N, C, H, W, ws, ws.numel())
+    _lib.call("slr_feature_cos_distance", f0.device, f0, f1, out, N, C, H, W, ws, ws.numel())
     return out
 
 
@@ -152,7 +152,7 @@ class PerceptualVGG16(nn.Module):
             raise ValueError(f"the perceptual metric needs H, W >= 16 (four 2x2 poolings), got {H} x {W}")
         x = torch.empty(2 * N, 3, H, W, device=img0.device, dtype=torch.float32)
         for t, part in ((img0, x[:N]), (img1, x[N:])):
-            nets._call("slr_vgg_prep", img0.device, t, u8, int(bool(from01)), part, N, H, W)
+            _lib.call("slr_vgg_prep", img0.device, t, u8, int(bool(from01)), part, N, H, W)
         per = [feature_distance(f[:N], f[N:]) for f in self.features(x)]
         val = 1.0 * per[0]                                                   # pretrained_networks.py:81-89, in its order
         for p in per[1:]:

@@ -219,14 +219,6 @@ def _fused_ok(*ts):
     return True
 
 
-def _call(name, device, *args):
-    """Entry point ``name`` of the library, looked up at every call, with ``args`` (tensors as their device pointers) and torch's
-    current stream on ``device``, run with ``device`` current; raises naming the entry point if it fails."""
-    args = [_lib.ptr(a) if torch.is_tensor(a) else a for a in args]
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), name)
-
-
 def _cached(owner, name, make, *tensors):
     """``make()``, kept in ``owner.__dict__[name]`` while ``tensors`` (what the value is derived from) keep their (data_ptr, _version,
     device): a move to another device, an in-place update (``load_state_dict``, ``copy_``) or a new tensor makes it again."""
@@ -242,7 +234,7 @@ def bn_relu_mask(x, scale, shift, mask):
     if _fused_ok(x, *([mask] if torch.is_tensor(mask) else [])):
         y = torch.empty_like(x)
         mc = -1 if mask is False else 0 if mask is None else mask.shape[1]
-        _call("slr_bn_relu_mask", x.device, x, scale, shift, mask if torch.is_tensor(mask) else None, mc, y, *x.shape)
+        _lib.call("slr_bn_relu_mask", x.device, x, scale, shift, mask if torch.is_tensor(mask) else None, mc, y, *x.shape)
         return y
     y = F.relu(x * scale.view(1, -1, 1, 1) - shift.view(1, -1, 1, 1))
     if mask is False:
@@ -258,8 +250,8 @@ def pconv_epilogue(raw0, bias, mask_box, mask_scale, winsize, residual=None, nex
         out = torch.empty_like(raw0)
         um = torch.empty_like(mask_box)
         sc, sh = next_bn if next_bn is not None else (None, None)
-        _call("slr_pconv_epilogue", raw0.device, raw0, bias, mask_box, float(mask_scale), residual, sc, sh, out, um, float(winsize),
-              *raw0.shape)
+        _lib.call("slr_pconv_epilogue", raw0.device, raw0, bias, mask_box, float(mask_scale), residual, sc, sh, out, um, float(winsize),
+                   *raw0.shape)
         return out, um
     um_raw = mask_box * mask_scale
     um = torch.clamp(um_raw, 0, 1)
@@ -347,7 +339,7 @@ class Conv(nn.Module):
             c.skip = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
         if partial:
             c.um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
-        _call(name, x.device, *args(c), layout)
+        _lib.call(name, x.device, *args(c), layout)
         return c
 
     def forward_skipout(self, x, pre_bn, skip_conv, layout=0):
@@ -382,11 +374,11 @@ class Conv(nn.Module):
             buf = torch.empty(nbytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
             if f32:
                 wscale = 1.0
-                _call(f"slr_{conv}_{'wino' if wino else 'f32'}_weights", w.device, w, buf, w.shape[0], w.shape[1])
+                _lib.call(f"slr_{conv}_{'wino' if wino else 'f32'}_weights", w.device, w, buf, w.shape[0], w.shape[1])
             else:
                 amax = float(w.abs().max())
                 wscale = 2.0 ** math.floor(math.log2(4096.0 / amax)) if amax > 0 else 1.0
-                _call(f"slr_{conv}_split_weights", w.device, w, buf, w.shape[0], w.shape[1], wscale)
+                _lib.call(f"slr_{conv}_split_weights", w.device, w, buf, w.shape[0], w.shape[1], wscale)
             return buf, wscale
         buf, wscale = _cached(self, "_w" + kind, make, w)
         return (buf, 1.0, 1.0, CONV_F32 | (CONV_WINO if wino else 0)) if f32 else (buf, wscale, _S.act_scale, 0)
@@ -411,14 +403,14 @@ class Conv(nn.Module):
             cout = self.weight.shape[0]
             out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
             assert not (layout & OUT_B8)
-            _call("slr_conv1x1_small", x.device, x, self.weight, bias, out, N, cin, cout, H, W, int(bool(layout & IN_B8)))
+            _lib.call("slr_conv1x1_small", x.device, x, self.weight, bias, out, N, cin, cout, H, W, int(bool(layout & IN_B8)))
             return out
         if self.k == 1 and _fused_ok(x):                 # the other 1x1 skip branches: split-f16 MFMA, HBM-bound
             N, cin, H, W = x.shape
             cout = self.weight.shape[0]
             buf, wscale, xscale, arith = self._split_weights()
             out = torch.empty(N, cout, H, W, device=x.device, dtype=x.dtype)
-            _call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, wscale, xscale, layout | arith)
+            _lib.call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, wscale, xscale, layout | arith)
             return out
         return F.conv2d(x, self.weight, bias, padding=self.pad)
 
@@ -482,7 +474,7 @@ def avgpool_down(x, b8=False):
     if _fused_ok(x):
         N, C, H, W = x.shape
         out = torch.empty(N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=x.dtype)
-        _call("slr_avgpool3x3s2", x.device, x, out, N, C, H, W, int(b8))
+        _lib.call("slr_avgpool3x3s2", x.device, x, out, N, C, H, W, int(b8))
         return out
     return F.avg_pool2d(x, 3, stride=2, padding=1)
 
@@ -492,7 +484,7 @@ def upsample_up(x, b8=False):
     if _fused_ok(x):
         N, C, H, W = x.shape
         out = torch.empty(N, C, 2 * H, 2 * W, device=x.device, dtype=x.dtype)
-        _call("slr_upsample_bilinear2x", x.device, x, out, N, C, H, W, int(b8))
+        _lib.call("slr_upsample_bilinear2x", x.device, x, out, N, C, H, W, int(b8))
         return out
     return F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
 
@@ -649,7 +641,7 @@ def saturation_count(device, reset=True):
     exact domain of the split, csrc/conv.hip).  The counter is one per device; the read is ordered on torch's current
     stream of that device and synchronises it with the host."""
     n = ctypes.c_ulonglong(0)
-    _call("slr_conv_saturation_count", device, ctypes.byref(n), 1 if reset else 0)
+    _lib.call("slr_conv_saturation_count", device, ctypes.byref(n), 1 if reset else 0)
     return int(n.value)
 
 
@@ -678,7 +670,7 @@ class SaturationLog:
         self._record()                                   # the value the clip starts from
 
     def _record(self):
-        _call("slr_conv_saturation_record", self.device, ctypes.c_void_p(self.slots.data_ptr() + 4 * self.n))
+        _lib.call("slr_conv_saturation_record", self.device, ctypes.c_void_p(self.slots.data_ptr() + 4 * self.n))
         self.n += 1
 
     def mark(self):
@@ -831,7 +823,7 @@ class Conv4x4s2(nn.Module):
 
         def make():
             buf = torch.empty(_lib.lib().slr_conv4x4s2_weight_bytes(w.shape[0], w.shape[1]), dtype=torch.uint8, device=w.device)
-            _call("slr_conv4x4s2_f32_weights", w.device, w, buf, w.shape[0], w.shape[1])
+            _lib.call("slr_conv4x4s2_f32_weights", w.device, w, buf, w.shape[0], w.shape[1])
             return buf
         return _cached(self, "_wfrag", make, w)
 
@@ -841,8 +833,8 @@ class Conv4x4s2(nn.Module):
             cout = self.weight.shape[0]
             out = torch.empty(N, cout, (H - 2) // 2 + 1, (W - 2) // 2 + 1, device=x.device, dtype=x.dtype)
             sc, sh = bn.scale_shift() if bn is not None else (None, None)
-            _call("slr_conv4x4s2_forward", x.device, x, self._frag(), self.bias, sc, sh, out, N, cin, cout, H, W, int(leaky is not None),
-                  float(leaky or 0.0))
+            _lib.call("slr_conv4x4s2_forward", x.device, x, self._frag(), self.bias, sc, sh, out, N, cin, cout, H, W, int(leaky is not None),
+                       float(leaky or 0.0))
             return out
         if leaky is not None:
             x = F.leaky_relu(x, leaky)
@@ -879,7 +871,7 @@ def instnorm_spade(x, gamma_beta, eps=1e-5):
     if _fused_ok(x, gamma_beta):
         N, C, H, W = x.shape
         out = torch.empty_like(x)
-        _call("slr_instnorm_spade", x.device, x, gamma_beta, out, N, C, H, W, float(eps))
+        _lib.call("slr_instnorm_spade", x.device, x, gamma_beta, out, N, C, H, W, float(eps))
         return out
     C = x.shape[1]
     return F.instance_norm(x, eps=eps) * (1 + gamma_beta[:, :C]) + gamma_beta[:, C:]
@@ -891,7 +883,7 @@ def resize_segmap(seg, k, nearest_channel=3):
     if _fused_ok(seg):
         N, C, H, W = seg.shape
         out = torch.empty(N, C, H >> k, W >> k, device=seg.device, dtype=seg.dtype)
-        _call("slr_resize_segmap", seg.device, seg, out, N, C, H, W, k, nearest_channel)
+        _lib.call("slr_resize_segmap", seg.device, seg, out, N, C, H, W, k, nearest_channel)
         return out
     size = (seg.shape[2] >> k, seg.shape[3] >> k)
     parts = [F.interpolate(seg[:, :nearest_channel], size=size, mode="bilinear", align_corners=False),
@@ -912,7 +904,7 @@ def upsample2x_concat(a, b=None, nearest_channel=-1, relu=RELU_NONE):
         N, Ca, H, W = a.shape
         Cb = 0 if b is None else b.shape[1]
         out = torch.empty(N, Ca + Cb, 2 * H, 2 * W, device=a.device, dtype=a.dtype)
-        _call("slr_upsample2x_concat", a.device, a, Ca, b, Cb, out, N, H, W, nearest_channel, relu)
+        _lib.call("slr_upsample2x_concat", a.device, a, Ca, b, Cb, out, N, H, W, nearest_channel, relu)
         return out
 
     def up(x):

@@ -6,8 +6,7 @@ Same public names, argument meaning, assertions and error behaviour as the refer
 """
 import torch
 
-from . import _lib
-from ._lib import WS_CLEAN, check, lib, ptr, require_device, stream_of, workspace
+from ._lib import WS_CLEAN, call, lib, require_device, workspace
 
 _MODES = {"summation": 0, "average": 1, "linear": 2, "softmax": 3}
 
@@ -28,9 +27,7 @@ def _splat_sum(input, flow):
     N, C, H, W = input.shape
     out = torch.empty_like(input)          # every element is written by the kernel (no memset)
     ws = workspace(input, "a", N, C, H, W)
-    with torch.cuda.device(input.device):
-        check(lib().slr_softsplat_forward(ptr(input), ptr(flow), ptr(out), N, C, H, W,
-                                          ptr(ws), ws.numel(), WS_CLEAN, stream_of(input)), "slr_softsplat_forward")
+    call("slr_softsplat_forward", input.device, input, flow, out, N, C, H, W, ws, ws.numel(), WS_CLEAN)
     return out
 
 
@@ -52,13 +49,10 @@ class _FunctionSoftsplat(torch.autograd.Function):
         gradInput = torch.empty_like(input) if self.needs_input_grad[0] == True else None
         gradFlow = torch.empty_like(flow) if self.needs_input_grad[1] == True else None
         if gradInput is not None or gradFlow is not None:
-            with torch.cuda.device(input.device):
-                # (channel groups -- 2-4 on the training crops, 2 on grids larger than the chip: partial gradFlow sums in a scratch tensor of torch's allocator)
-                nb = int(lib().slr_softsplat_backward_ws_bytes(N, C, H, W)) if gradFlow is not None else 0
-                ws = torch.empty(nb, dtype=torch.uint8, device=input.device) if nb else None
-                check(lib().slr_softsplat_backward_ws(ptr(input), ptr(flow), ptr(gradOutput), ptr(gradInput),
-                                                      ptr(gradFlow), N, C, H, W, ptr(ws), nb, stream_of(input)),
-                      "slr_softsplat_backward_ws")
+            # (channel groups -- 2-4 on the training crops, 2 on grids larger than the chip: partial gradFlow sums in a scratch tensor of torch's allocator)
+            nb = int(lib().slr_softsplat_backward_ws_bytes(N, C, H, W)) if gradFlow is not None else 0
+            ws = torch.empty(nb, dtype=torch.uint8, device=input.device) if nb else None
+            call("slr_softsplat_backward_ws", input.device, input, flow, gradOutput, gradInput, gradFlow, N, C, H, W, ws, nb)
         return gradInput, gradFlow
 
 
@@ -107,11 +101,8 @@ def FunctionSoftsplat(tenInput, tenFlow, tenMetric, strType):
     N, C, H, W = tenInput.shape
     out = torch.empty_like(tenInput)
     ws = workspace(tenInput, "a", N, C, H, W)
-    with torch.cuda.device(tenInput.device):
-        check(lib().slr_softsplat_mode_forward(ptr(tenInput), ptr(tenMetric) if strType != 'average' else None,
-                                               ptr(tenFlow), ptr(out), N, C, H, W, _MODES[strType],
-                                               ptr(ws), ws.numel(), WS_CLEAN, stream_of(tenInput)),
-              "slr_softsplat_mode_forward")
+    call("slr_softsplat_mode_forward", tenInput.device, tenInput, tenMetric if strType != 'average' else None, tenFlow, out,
+         N, C, H, W, _MODES[strType], ws, ws.numel(), WS_CLEAN)
     return out
 
 
@@ -131,9 +122,7 @@ def _maxsplat(input, flow, init):
     N, C, H, W = input.shape
     out = torch.empty_like(input)
     ws = workspace(input, "a", N, C, H, W)
-    with torch.cuda.device(input.device):
-        check(lib().slr_maxsplat_forward(ptr(input), ptr(flow), ptr(out), float(init), N, C, H, W,
-                                         ptr(ws), ws.numel(), WS_CLEAN, stream_of(input)), "slr_maxsplat_forward")
+    call("slr_maxsplat_forward", input.device, input, flow, out, float(init), N, C, H, W, ws, ws.numel(), WS_CLEAN)
     return out
 
 
@@ -154,9 +143,7 @@ def _FunctionMaximumWarpNormsplat(input, flow):
     scratch = torch.empty_like(input)
     out = torch.empty_like(input)
     ws = workspace(input, "a", N, C, H, W)
-    with torch.cuda.device(input.device):
-        check(lib().slr_max_warp_norm(ptr(input), ptr(flow), ptr(scratch), ptr(out), N, C, H, W,
-                                      ptr(ws), ws.numel(), WS_CLEAN, stream_of(input)), "slr_max_warp_norm")
+    call("slr_max_warp_norm", input.device, input, flow, scratch, out, N, C, H, W, ws, ws.numel(), WS_CLEAN)
     return out
 
 
@@ -186,8 +173,5 @@ def splat_normalize(accum, norm_mode="zero_to_one", eps=1e-8):
     require_device(accum)
     N, C1, H, W = accum.shape
     out = accum.new_empty(N, C1 - 1, H, W)
-    with torch.cuda.device(accum.device):
-        check(lib().slr_splat_normalize(ptr(accum), ptr(out), N, C1 - 1, H, W,
-                                        0 if norm_mode == "zero_to_one" else 1, float(eps), stream_of(accum)),
-              "slr_splat_normalize")
+    call("slr_splat_normalize", accum.device, accum, out, N, C1 - 1, H, W, 0 if norm_mode == "zero_to_one" else 1, float(eps))
     return out

@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from ._lib import check, lib, ptr, require_device, stream_of, workspace
+from ._lib import call, check, lib, require_device
 from .euler_integration_manipulator import euler_integration_all
 
 
@@ -57,56 +57,13 @@ def _arm_timer(t, frames=1):
     kernel_timing.append((ev[0], ev[1], frames))
 
 
-def bin_flow(flow, C, role):
-    """Sort the source pixels of ``flow`` [1,2,H,W] into output-tile bins (slr_splat_bin).
-    Returns the workspace; valid until the next bin_flow with the same role/shape/stream."""
-    require_device(flow)
-    N, _, H, W = flow.shape
-    ws = workspace(flow, role, N, C, H, W)
-    with torch.cuda.device(flow.device):
-        check(lib().slr_splat_bin(ptr(flow), N, H, W, ptr(ws), ws.numel(), stream_of(flow)), "slr_splat_bin")
-    return ws
-
-
-def bin_flow_pair(flow_a, flow_b, C):
-    """bin_flow for the forward and the backward displacement map of a frame in one go."""
-    require_device(flow_a, flow_b)
-    assert flow_a.shape == flow_b.shape
-    N, _, H, W = flow_a.shape
-    ws_a, ws_b = workspace(flow_a, "f", N, C, H, W), workspace(flow_a, "p", N, C, H, W)
-    with torch.cuda.device(flow_a.device):
-        check(lib().slr_splat_bin_pair(ptr(flow_a), ptr(flow_b), N, H, W, ptr(ws_a), ptr(ws_b), ws_a.numel(),
-                                       stream_of(flow_a)), "slr_splat_bin_pair")
-    return ws_a, ws_b
-
-
 def global_max(x):
     """x.max() as a 1-element device tensor, no host sync (animating_softmax_splating.py:855)."""
     require_device(x)
     res = x.new_empty(1)
     scratch = x.new_empty(1024)
-    with torch.cuda.device(x.device):
-        check(lib().slr_global_max(ptr(x), x.numel(), ptr(res), ptr(scratch), stream_of(x)), "slr_global_max")
+    call("slr_global_max", x.device, x, x.numel(), res, scratch)
     return res
-
-
-def synth_group(values, wlogit, disp_f, disp_p, alpha, ws_f, ws_p, wmax=None, exp_weights=True,
-                eps=1e-8, return_norm=False, timed=False):
-    """out = [splat(values*w*alpha, disp_f) + splat(values*w*(1-alpha), disp_p)] / max(same for w, eps)
-    with w = exp(wlogit - wmax) | exp(wlogit) | wlogit.  values [1,C,H,W], wlogit [1,1,H,W]."""
-    require_device(values, wlogit, disp_f, disp_p, wmax)
-    assert values.shape[0] == 1 and wlogit.shape[1] == 1 and disp_f.shape[1] == 2 and disp_p.shape[1] == 2
-    _, C, H, W = values.shape
-    out = torch.empty_like(values)
-    norm = values.new_empty(1, 1, H, W) if return_norm else None
-    with torch.cuda.device(values.device):
-        if timed and kernel_timing is not None:
-            _arm_timer(values)
-        check(lib().slr_synth_group(ptr(values), ptr(wlogit), ptr(wmax), 1 if exp_weights else 0,
-                                    ptr(disp_f), ptr(disp_p), float(alpha), ptr(out), ptr(norm),
-                                    C, H, W, float(eps), ptr(ws_f), ptr(ws_p), ws_f.numel(),
-                                    stream_of(values)), "slr_synth_group")
-    return (out, norm) if return_norm else out
 
 
 VALUES_B4 = 2         # include/slr_splat.h: SLR_SYNTH_VALUES_B4
@@ -149,10 +106,7 @@ class MotionPlan:
         plan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         idx_f = torch.tensor(ts, dtype=torch.int32, device=dev)
         idx_p = (self.N - idx_f).to(torch.int32)
-        with torch.cuda.device(dev):
-            check(L.slr_clip_plan_build(ptr(self.disp_f), ctypes.c_void_p(idx_f.data_ptr()), ptr(self.disp_p),
-                                        ctypes.c_void_p(idx_p.data_ptr()), n, self.H, self.W, ptr(plan), nbytes,
-                                        stream_of(plan)), "slr_clip_plan_build")
+        call("slr_clip_plan_build", dev, self.disp_f, idx_f, self.disp_p, idx_p, n, self.H, self.W, plan, nbytes)
         off, stride = ctypes.c_size_t(), ctypes.c_int()
         check(L.slr_clip_plan_totals(n, self.H, self.W, ctypes.byref(off), ctypes.byref(stride)), "slr_clip_plan_totals")
         totals = plan[off.value:off.value + n * stride.value * 4].view(torch.int32).view(n, stride.value)
@@ -184,32 +138,18 @@ class MotionPlan:
 
 def synth_group_clip(values, wlogit, mp, t, alpha, wmax=None, exp_weights=True, eps=1e-8, return_norm=False, timed=False,
                      out=None, values_b4=None):
-    """synth_group for frame t of a MotionPlan (bins and work plan prepared per clip).
+    """out = [splat(values*w*alpha, disp_f) + splat(values*w*(1-alpha), disp_p)] / max(same for w, eps) for frame t of a MotionPlan,
+    with w = exp(wlogit - wmax) | exp(wlogit) | wlogit.  values [1,C,H,W], wlogit [1,1,H,W]: synth_group_clip_batch with one frame.
     out: optional [1,C,H,W] destination (e.g. one sample of a batch buffer the decoder will read)."""
-    require_device(values, wlogit, wmax)
-    assert values.shape[0] == 1 and wlogit.shape[1] == 1
-    _, C, H, W = values.shape
-    plan, n, i, n_items = mp.lookup(t)
-    disp_f, disp_p = mp.disp_f[t], mp.disp_p[mp.N - t]
     if out is None:
         out = torch.empty_like(values)
-    else:
-        require_device(out)
-        assert out.shape == values.shape and out.device == values.device
-    norm = values.new_empty(1, 1, H, W) if return_norm else None
-    with torch.cuda.device(values.device):
-        if timed and kernel_timing is not None:
-            _arm_timer(values)
-        flags = (1 if exp_weights else 0) | (VALUES_B4 if values_b4 is not None else 0)
-        check(lib().slr_synth_group_clip(ptr(values if values_b4 is None else values_b4), ptr(wlogit), ptr(wmax), flags,
-                                         ptr(disp_f), ptr(disp_p), float(alpha), ptr(out), ptr(norm), C, H, W,
-                                         float(eps), ptr(plan), plan.numel(), n, i, n_items, stream_of(values)), "slr_synth_group_clip")
+    norm = values.new_empty(1, 1, *values.shape[2:]) if return_norm else None
+    synth_group_clip_batch(values, wlogit, mp, [t], [alpha], [out], wmax=wmax, exp_weights=exp_weights, eps=eps, timed=timed,
+                           values_b4=values_b4, norm_outs=[norm] if return_norm else None)
     return (out, norm) if return_norm else out
 
 
 MAX_BATCH = min(16, max(1, int(os.environ.get("SLR_SFS_AMD_SPLAT_BATCH", "16"))))   # frames per launch of slr_synth_group_clip_batch (csrc: SLR_CLIP_MAXB = 16; 8 / 12 / 16: 158 / 153 / 151-153 us per frame of work)
-
-
 
 
 def pack_planes4(values):
@@ -219,55 +159,55 @@ def pack_planes4(values):
     assert values.is_contiguous() and values.shape[1] % 4 == 0
     out = torch.empty_like(values)
     N, C, H, W = values.shape
-    with torch.cuda.device(values.device):
-        check(lib().slr_pack_planes4(ptr(values), ptr(out), N, C, H, W, stream_of(values)), "slr_pack_planes4")
+    call("slr_pack_planes4", values.device, values, out, N, C, H, W)
     return out
 
 
 def synth_group_clip_batch(values, wlogit, mp, ts, alphas, outs, wmax=None, exp_weights=True, eps=1e-8, timed=False,
-                           group2=None, values_b4=None):
+                           group2=None, values_b4=None, norm_outs=None):
     """synth_group_clip for up to MAX_BATCH frames `ts` of ONE chunk of a MotionPlan in one launch of the tile kernel:
     outs[k] ([1,C,H,W], e.g. the samples of a decoder batch) receives frame ts[k].
     group2 = (values2 [1,1,H,W], wlogit2 [1,1,H,W], outs2): a second weight group (exp weights) splatted by the same launch
     with the same records -- the 2-layer model's alpha plane (slr_synth_two_groups_clip_batch).
-    values_b4: pack_planes4(values) -- the kernel then reads that copy (same results, a quarter of the plane loads)."""
-    require_device(values, wlogit, wmax, *outs)
+    values_b4: pack_planes4(values) -- the kernel then reads that copy (same results, a quarter of the plane loads).
+    norm_outs: optional [1,1,H,W] tensors, one per frame, that receive the frames' normalisers (not with group2)."""
+    require_device(values, wlogit, wmax, *outs, *(norm_outs or ()))
     assert values.shape[0] == 1 and wlogit.shape[1] == 1 and 1 <= len(ts) <= MAX_BATCH and len(outs) == len(ts)
     _, C, H, W = values.shape
     look = [mp.lookup(t) for t in ts]
     plan, n = look[0][0], look[0][1]
     assert all(lk[0] is plan for lk in look), "frames of one launch must come from one chunk of the plan"
     nb = len(ts)
-    L = lib()
     PP = ctypes.c_void_p * nb
     df = PP(*[mp.disp_f[t].data_ptr() for t in ts])
     dp = PP(*[mp.disp_p[mp.N - t].data_ptr() for t in ts])
     op = PP(*[o.data_ptr() for o in outs])
+    assert norm_outs is None or (group2 is None and len(norm_outs) == nb)
+    no = None if norm_outs is None else PP(*[o.data_ptr() for o in norm_outs])
     al = (ctypes.c_float * nb)(*[float(a) for a in alphas])
     fr = (ctypes.c_int * nb)(*[lk[2] for lk in look])
     n_items = (ctypes.c_int * nb)(*[lk[3] for lk in look])
     for o in outs:
         assert o.shape == values.shape and o.device == values.device
+    for o in norm_outs or ():
+        assert o.shape == (1, 1, H, W) and o.device == values.device
     flags = (1 if exp_weights else 0) | (VALUES_B4 if values_b4 is not None else 0)
     vsrc = values if values_b4 is None else values_b4
     assert vsrc.shape == values.shape and vsrc.device == values.device
-    with torch.cuda.device(values.device):
-        if timed and kernel_timing is not None:
-            _arm_timer(values, nb)
-        if group2 is None:
-            check(L.slr_synth_group_clip_batch(ptr(vsrc), ptr(wlogit), ptr(wmax), flags, df, dp, al, op,
-                                               None, C, H, W, float(eps), ptr(plan), plan.numel(), n, fr, nb, n_items,
-                                               stream_of(values)), "slr_synth_group_clip_batch")
-        else:
-            v2, w2, outs2 = group2
-            require_device(v2, w2, *outs2)
-            assert v2.shape == (1, 1, H, W) and w2.shape == (1, 1, H, W) and len(outs2) == nb
-            assert all(o.shape == (1, 1, H, W) and o.is_contiguous() for o in outs2)
-            op2 = PP(*[o.data_ptr() for o in outs2])
-            check(L.slr_synth_two_groups_clip_batch(ptr(vsrc), ptr(wlogit), ptr(wmax), flags, ptr(v2), ptr(w2), 1,
-                                                    df, dp, al, op, op2, C, H, W, float(eps), ptr(plan), plan.numel(), n, fr, nb,
-                                                    n_items, stream_of(values)),
-                  "slr_synth_two_groups_clip_batch")
+    if group2 is not None:
+        v2, w2, outs2 = group2
+        require_device(v2, w2, *outs2)
+        assert v2.shape == (1, 1, H, W) and w2.shape == (1, 1, H, W) and len(outs2) == nb
+        assert all(o.shape == (1, 1, H, W) and o.is_contiguous() for o in outs2)
+        op2 = PP(*[o.data_ptr() for o in outs2])
+    if timed and kernel_timing is not None:
+        _arm_timer(values, nb)
+    if group2 is None:
+        call("slr_synth_group_clip_batch", values.device, vsrc, wlogit, wmax, flags, df, dp, al, op, no, C, H, W, float(eps),
+             plan, plan.numel(), n, fr, nb, n_items)
+    else:
+        call("slr_synth_two_groups_clip_batch", values.device, vsrc, wlogit, wmax, flags, v2, w2, 1, df, dp, al, op, op2, C, H, W,
+             float(eps), plan, plan.numel(), n, fr, nb, n_items)
     return outs
 
 

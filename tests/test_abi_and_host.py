@@ -32,6 +32,45 @@ def test_header_symbols_exported(L):
     assert L.slr_abi_version() == slr_sfs_amd._lib.ABI_VERSION == int(m.group(1))
 
 
+def _c_class(ctype):
+    """The class of a C type as the header spells it: 'pointer', 'int', 'float', 'size_t' or 'void'; anything else raises."""
+    words = [w for w in re.findall(r"\w+|\*", ctype) if w != "const"]
+    if "*" in words:
+        return "pointer"
+    assert words in (["int"], ["float"], ["size_t"], ["void"]), f"header type {ctype!r} is not classified"
+    return words[0]
+
+
+def _ctypes_class(t):
+    """The same classes for an entry of the signature table."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}[t]
+
+
+def test_signature_table_agrees_with_header_types():
+    """Every prototype of include/slr_splat.h against _lib.SIGNATURES: the return type, the number of arguments and the class of each
+    (pointer / int / float / size_t).  Reads the table only -- the library need not be built."""
+    from slr_sfs_amd._lib import SIGNATURES
+    hdr = open(os.path.join(ROOT, "include", "slr_splat.h")).read()
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+    hdr = re.sub(r"^\s*#.*$|extern\s+\"C\"\s*\{", " ", hdr, flags=re.M)
+    protos = re.findall(r"([\w\s\*]+?)\b(slr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(protos) == len(set(p[1] for p in protos)) == len(re.findall(r"\bslr_[a-z0-9_]+\s*\(", hdr)), "a prototype was not parsed"
+    assert set(p[1] for p in protos) == set(SIGNATURES)
+    for ret, name, params in protos:
+        restype, argtypes = SIGNATURES[name]
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        # a parameter is `type name`: the name is the last word, everything before it (the `*` included) the type
+        declared = [_c_class(re.match(r"(.*?)(\w+)$", p, re.S).group(1)) for p in params]
+        assert _ctypes_class(restype) == _c_class(ret), (name, "return", ret, restype)
+        assert len(argtypes) == len(declared), (name, len(argtypes), len(declared))
+        for k, (a, d) in enumerate(zip(argtypes, declared)):
+            assert _ctypes_class(a) == d, (name, k, params[k], a)
+
+
 def test_workspace_size_and_argument_errors(L):
     # (row-segment lists: 256 records of 8 bytes per tile and list, three lists + plans -- 12.7 MB at 768x1280; the per-pixel bins of
     #  rounds 1-3 took 12 bytes per source pixel + partial tiles: ~300 MB)

@@ -109,7 +109,7 @@ def main():
         ms = time_ms(lambda: metrics.perceptual_sim(xb, yb, net), a.iters, a.warmup) / B
         prep = torch.empty(2 * B, 3, H, W, device=dev)
         for t, part in ((xb, prep[:B]), (yb, prep[B:])):
-            metrics.nets._call("slr_vgg_prep", dev, t, 1, 1, part, B, H, W)
+            metrics._lib.call("slr_vgg_prep", dev, t, 1, 1, part, B, H, W)
         ms_feat = time_ms(lambda: net.features(prep), a.iters, a.warmup) / B
         feats = net.features(prep)
         pools = [metrics.relu_maxpool2x2(f) for f in feats[:4]]
