@@ -380,9 +380,13 @@ def test_function_softsplat_modes_golden(S, golden_dir):
 
 
 def test_function_softsplat_modes_autograd_path_matches_fused(S):
+    """The differentiable composition gives the fused kernel's output, and its gradients w.r.t. input, flow and metric are those of
+    the float64 definition (tests/test_gpu_gradients.py: check_mode_gradients, its criterion and its condition on the inputs)."""
+    from test_gpu_gradients import check_mode_gradients
     rng = np.random.default_rng(3)
     x, fl = dev(rng.standard_normal((1, 6, 40, 72))), dev(rng.uniform(-3, 3, (1, 2, 40, 72)))
     met = dev(rng.standard_normal((1, 1, 40, 72)))
+    go = rng.standard_normal((1, 6, 40, 72)).astype(np.float32)
     for mode in ("average", "linear", "softmax"):
         m = met.abs() + 0.1 if mode == "linear" else met
         fused = S.FunctionSoftsplat(x, fl, m, mode)
@@ -391,6 +395,7 @@ def test_function_softsplat_modes_autograd_path_matches_fused(S):
         np.testing.assert_allclose(host(comp), host(fused), rtol=1e-4, atol=1e-5)
         comp.sum().backward()
         assert torch.isfinite(xg.grad).all()
+        assert check_mode_gradients(S, host(x), host(fl), host(m), mode, go, "parity 1x6x40x72"), "condition on the inputs"
 
 
 def test_max_splat_family_golden(S, golden_dir):
