@@ -90,6 +90,61 @@ def test_workspace_size_and_argument_errors(L):
     assert rc == -1
 
 
+def test_metric_entry_points_refuse_bad_arguments(L):
+    """The five entry points of csrc/metrics.hip: every argument check returns -1 and names the argument before anything touches a device
+    (the pointers are dummy integers -- nothing dereferences them on these paths), and the workspace sizes are the documented ones."""
+    P, N, C, H, W = 0x10000, 3, 3, 720, 1280                   # a 16-byte aligned non-null "pointer"
+    need = L.slr_ssim_ws_bytes(N, H, W)
+    assert need == 3 * 20 * 45 * 3 * 8                         # [N][tiles of 16 x 64][3] doubles
+    assert L.slr_ssim_ws_bytes(0, H, W) == 0 and L.slr_ssim_ws_bytes(N, 0, W) == 0
+    assert L.slr_ssim_ws_bytes(1, 17, 65) == 2 * 2 * 3 * 8     # one past the tile in both directions
+
+    def refused(rc, *words):
+        msg = L.slr_last_error()
+        assert rc == -1 and all(w in msg for w in words), (rc, msg)
+
+    def ssim(img1=P, img2=P, u8=1, mask=None, out=P, N=N, C=C, H=H, W=W, window=11, ws=P, ws_bytes=need):
+        return L.slr_ssim_mse(img1, img2, u8, mask, out, N, C, H, W, window, ws, ws_bytes, None)
+
+    for window in (0, 10, 17, -1, 2):
+        refused(ssim(window=window), b"slr_ssim_mse", b"window_size")
+    for kw in ({"C": 0}, {"C": 65}, {"N": 65536}, {"N": 0}, {"H": 0}, {"W": -1}):
+        refused(ssim(**kw), b"slr_ssim_mse", b"sizes")
+    for name in ("img1", "img2", "out", "ws"):
+        refused(ssim(**{name: None}), b"slr_ssim_mse", b"null")
+    refused(ssim(ws_bytes=need - 1), b"slr_ssim_mse", b"ws")
+    refused(ssim(ws_bytes=0), b"slr_ssim_mse", b"ws")
+    refused(ssim(ws=P + 4), b"slr_ssim_mse", b"ws", b"aligned")
+
+    refused(L.slr_vgg_prep(P, 1, 0, P, 1, 64, 96, None), b"slr_vgg_prep", b"from01")
+    refused(L.slr_vgg_prep(None, 1, 1, P, 1, 64, 96, None), b"slr_vgg_prep", b"null")
+    refused(L.slr_vgg_prep(P, 0, 1, None, 1, 64, 96, None), b"slr_vgg_prep", b"null")
+    refused(L.slr_vgg_prep(P, 0, 1, P, 0, 64, 96, None), b"slr_vgg_prep", b"sizes")
+
+    refused(L.slr_relu_maxpool2x2_b8(P, P, 1, 12, 8, 8, None), b"slr_relu_maxpool2x2_b8", b"C % 8")
+    refused(L.slr_relu_maxpool2x2_b8(P, P, 1, 8, 1, 8, None), b"slr_relu_maxpool2x2_b8", b"H, W >= 2")
+    refused(L.slr_relu_maxpool2x2_b8(P, P, 1, 8, 8, 1, None), b"slr_relu_maxpool2x2_b8", b"H, W >= 2")
+    refused(L.slr_relu_maxpool2x2_b8(P + 8, P, 1, 8, 8, 8, None), b"slr_relu_maxpool2x2_b8", b"16-byte")
+    refused(L.slr_relu_maxpool2x2_b8(P, P + 8, 1, 8, 8, 8, None), b"slr_relu_maxpool2x2_b8", b"16-byte")
+    refused(L.slr_relu_maxpool2x2_b8(None, P, 1, 8, 8, 8, None), b"slr_relu_maxpool2x2_b8", b"null")
+
+    fneed = L.slr_feature_cos_ws_bytes(2, 45, 80)
+    assert fneed == 2 * 15 * 8                                 # [N][blocks of 256 pixels] doubles: 3600 pixels -> 15 blocks
+    assert L.slr_feature_cos_ws_bytes(1, 1, 257) == 2 * 8 and L.slr_feature_cos_ws_bytes(0, 45, 80) == 0
+
+    def fd(f0=P, f1=P, out=P, N=2, C=64, H=45, W=80, ws=P, ws_bytes=fneed):
+        return L.slr_feature_cos_distance(f0, f1, out, N, C, H, W, ws, ws_bytes, None)
+
+    refused(fd(C=12), b"slr_feature_cos_distance", b"C % 8")
+    refused(fd(C=0), b"slr_feature_cos_distance", b"sizes")
+    refused(fd(N=65536, ws_bytes=1 << 40), b"slr_feature_cos_distance", b"sizes")
+    refused(fd(ws_bytes=fneed - 1), b"slr_feature_cos_distance", b"ws")
+    refused(fd(ws=P + 4), b"slr_feature_cos_distance", b"ws")
+    refused(fd(f1=P + 8), b"slr_feature_cos_distance", b"16-byte")
+    for name in ("f0", "f1", "out", "ws"):
+        refused(fd(**{name: None}), b"slr_feature_cos_distance", b"null")
+
+
 def test_operators_refuse_cpu_tensors_and_have_no_fallback():
     import slr_sfs_amd as S
     z = torch.zeros

@@ -90,9 +90,11 @@ def test_perceptual_vs_reference(M, ref, vgg, hw):
 
 def test_perceptual_256x384_vs_fp64(M, vgg):
     a_u8, b_u8 = MF.image_pair(256, 384, n=1, tag="vgg256")
-    got = M.perceptual_sim(torch.from_numpy(a_u8).cuda(), torch.from_numpy(b_u8).cuda(), vgg)
-    want = MF.perceptual_f64(MF.to_tensor(a_u8), MF.to_tensor(b_u8))
+    got, per = vgg.score(torch.from_numpy(a_u8).cuda(), torch.from_numpy(b_u8).cuda(), True, retPerLayer=True)
+    assert torch.equal(got, M.perceptual_sim(torch.from_numpy(a_u8).cuda(), torch.from_numpy(b_u8).cuda(), vgg))
+    want, want_per = MF.perceptual_f64(MF.to_tensor(a_u8), MF.to_tensor(b_u8), per_layer=True)
     np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=1e-4)
+    np.testing.assert_allclose(torch.stack(per).cpu().numpy(), torch.stack(want_per).numpy(), rtol=1e-4)      # each slice, not only their sum
 
 
 def test_relu_maxpool_odd_sizes(M):
