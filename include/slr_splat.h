@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 12
+#define SLR_ABI_VERSION 13
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -269,6 +269,40 @@ int slr_softsplat_backward(const float *in, const float *flow, const float *grad
 size_t slr_softsplat_backward_ws_bytes(int N, int C, int H, int W);
 int slr_softsplat_backward_ws(const float *in, const float *flow, const float *grad_out, float *grad_in,
                               float *grad_flow, int N, int C, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ splat: the two-direction blend of the training step */
+
+/* The splat half of the training step as one differentiable operator.  Replaces the weighting, the two `cat`, the two 65-plane
+ * summation splats, the in-place adds, the clamp and the division of animating_softmax_splating.py:587-692 and autograd's mirror image
+ * of them.  Per sample b and direction d (f: start features along disp_f, p: end features along disp_p):
+ *   w_d = exp(clamp(logits_d - zmax_d[0], clamp_lo, clamp_hi)) * a_d,   a_f = alpha[b], a_p = 1 - alpha[b]
+ *   out = (splat(values_f w_f, disp_f) + splat(values_p w_p, disp_p)) / max(norm, eps),   norm = splat(w_f, disp_f) + splat(w_p, disp_p)
+ *   values_d [N,C,H,W];  logits_d [N,1,H,W] or NULL (w_d = a_d; "train_Z" off);  disp_d [N,2,H,W];  alpha [N] ON THE DEVICE;
+ *   zmax_d: device scalar (slr_global_max of logits_d, :601 / :646) or NULL (nothing subtracted: use_softmax_splatter_v1);
+ *   no clamp ("no_clamp_Z"): clamp_lo = -INFINITY, clamp_hi = INFINITY;  eps 1e-8 (:691).
+ *   out [N,C,H,W], norm [N,1,H,W]: every element written here; a destination nobody reaches: norm 0, out exactly +0.0.
+ *   splat_ws / ws_flags: the workspace of slr_softsplat_forward (16-byte aligned; the two directions use it one after the other; not SLR_WS_PREBINNED);
+ *   scratch: slr_splat_blend_ws_bytes(N, C, H, W) bytes, 16-byte aligned -- the forward's raw sums per direction (two [N,C,H,W]
+ *   stacks and two normaliser planes; the weights are applied inside the tile kernels: no weighted stack), the backward's partial sums (0 for a non-positive size: host arithmetic only).  Nothing in it outlives a call:
+ *   what the backward needs is the inputs, `out` and `norm`. */
+size_t slr_splat_blend_ws_bytes(int N, int C, int H, int W);
+int slr_splat_blend_forward(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
+                            const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
+                            const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
+                            int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags,
+                            void *scratch, size_t scratch_bytes, void *stream);
+
+/* Its backward for grad_out = dL/dout [N,C,H,W], with `out` and `norm` as the forward wrote them.  Any of the six gradient pointers may
+ * be NULL (needs_input_grad); the others are bit-identical to the call that asks for all six.  grad_logits_d needs logits_d; it is
+ * zero where the clamp bites, and the element that holds the maximum (the first one in memory: ties are not split) also receives
+ * minus the sum of all the others' -- reduced per workgroup in float64, then in a fixed order: no float atomics, the same bits from
+ * run to run.  A source whose target coordinate is not representable has gradient exactly 0 everywhere. */
+int slr_splat_blend_backward(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
+                             const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
+                             const float *zmax_p, float clamp_lo, float clamp_hi, float eps, const float *out,
+                             const float *norm, const float *grad_out, float *grad_values_f, float *grad_logits_f,
+                             float *grad_disp_f, float *grad_values_p, float *grad_logits_p, float *grad_disp_p,
+                             int N, int C, int H, int W, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------ maximum-splat family */
 

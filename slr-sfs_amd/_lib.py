@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 12
+ABI_VERSION = 13
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -43,6 +43,9 @@ SIGNATURES = {
     "slr_softsplat_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "slr_softsplat_backward_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "slr_softsplat_backward_ws": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_splat_blend_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "slr_splat_blend_forward": (_i, [_fp] * 9 + [_f, _f, _f, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp]),
+    "slr_splat_blend_backward": (_i, [_fp] * 9 + [_f, _f, _f] + [_fp] * 9 + [_i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_maxsplat_forward": (_i, [_fp, _fp, _fp, _f, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
     "slr_max_warp_norm": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
     "slr_bn_relu_mask": (_i, [_fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _vp]),

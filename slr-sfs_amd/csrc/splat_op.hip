@@ -405,8 +405,8 @@ struct OpArgs {
 // rows front end.  grid.x: a multiple of 8 * SLR_XCD_GROUP blocks covering the plan's items (surplus workgroups exit at once).
 // PASSES = false: one piece per workgroup, no loop over work (80 VGPRs: three workgroups per CU); a piece of more than SEG entries is
 // appended to the deferred list.  PASSES = true: OP_DEFER_WG workgroups walk the deferred list pass by pass (normally it is empty).
-template <bool NORM, bool MAXOP, bool PASSES>
-__global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_kernel(OpArgs a) {
+template <bool NORM, bool MAXOP, bool PASSES, bool RAW>
+__device__ __forceinline__ void op_rows_body(const OpArgs &a) {
     using Cfg = std::conditional_t<PASSES, OpPassCfg, OpCfg>;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const TileLds<Cfg> L(smem);
@@ -436,13 +436,13 @@ __global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_kerne
 #ifdef SLR_TRACE
         T_NOTE(s, 58, t_entry);
 #endif
-        if (!rows_piece_once<Cfg, false, NORM, MAXOP, false>(s, f, L, p, tid, k, cb, ce) && tid == 0 && blockIdx.y == 0)
+        if (!rows_piece_once<Cfg, false, NORM, MAXOP, false, RAW>(s, f, L, p, tid, k, cb, ce) && tid == 0 && blockIdx.y == 0)
             f.defer[atomicAdd(f.totals + 4, 1u)] = at;     // (one entry per piece: every channel group gets here)
         T_NOTE(s, 57, wall_clock64());
     } else {
         const uint32_t ndef = has_planes ? f.totals[4] : 0u;
         for (uint32_t q = blockIdx.x; q < ndef; q += gridDim.x)
-            rows_piece_passes<Cfg, false, NORM, MAXOP, false>(s, f, L, make_piece<Cfg>(s, f.items[f.defer[q]]), tid, k, cb, ce);
+            rows_piece_passes<Cfg, false, NORM, MAXOP, false, RAW>(s, f, L, make_piece<Cfg>(s, f.items[f.defer[q]]), tid, k, cb, ce);
         // the last workgroup to get here empties the deferred list for the plan's next use (prebinned calls share one plan).  EVERY
         // workgroup of the grid arrives -- also those whose channel group is empty (C = 36, 65, 72, 80 with 8 groups): counting only some
         // of them left the list in place for the next prebinned call, which then walked the same pieces again
@@ -538,8 +538,8 @@ __device__ __forceinline__ uint32_t scan_collect(const TileShared &s, const Tile
 // follows (normally empty) renders it with many workgroups at once.
 // (Measured and rejected in rounds 4 / 5: the deferred pieces as TAIL blocks of the same launch behind an arrival counter -- config C2
 //  37 -> 49.5 us, 512 arrival atomics on one word ~ 20 us; column pieces in the first launch: every piece repeats the candidate walk.)
-template <bool NORM, bool MAXOP>
-__global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_kernel(OpArgs a) {
+template <bool NORM, bool MAXOP, bool RAW>
+__device__ __forceinline__ void op_scan_body(const OpArgs &a) {
     using Cfg = ScanCfg;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const TileLds<Cfg> L(smem);
@@ -568,9 +568,9 @@ __global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_kernel(OpArgs a) {
         PixelSums sums = {0.0f, 0.0f, 0.0f};
         EntryRegs<Cfg> e;
         float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-        build_records<Cfg, NORM, false>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+        build_records<Cfg, NORM, false, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
         T_STAMP(s, 6);
-        stream_planes<Cfg, NORM, MAXOP, false, false, false, true>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
+        stream_planes<Cfg, NORM, MAXOP, false, false, false, true, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
         T_STAMP(s, 59);
         return;
     }
@@ -623,8 +623,8 @@ constexpr uint32_t SINK_P = SLR_SINK_PIECES, SINK_T = SLR_SINK_TASKS, SINK_MINE 
 #define SINK_STAMP(slot, v) do { } while (0)
 #endif
 static_assert(SINK_T <= 16, "slab bits of the arrival word");
-template <bool NORM, bool MAXOP>
-__global__ __launch_bounds__(TT, 4) void op_sink_kernel(OpArgs a) {
+template <bool NORM, bool MAXOP, bool RAW>
+__device__ __forceinline__ void op_sink_body(const OpArgs &a) {
     using Cfg = ScanCfg;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t mine[2 * SINK_MINE];              // this workgroup's tasks of a candidate block (build_records overwrites the list)
@@ -785,9 +785,9 @@ __global__ __launch_bounds__(TT, 4) void op_sink_kernel(OpArgs a) {
                 EntryRegs<Cfg> e;
                 float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
                 SINK_STAMP(5, wall_clock64());
-                build_records<Cfg, NORM, false>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+                build_records<Cfg, NORM, false, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
                 SINK_STAMP(6, wall_clock64());
-                stream_planes<Cfg, NORM, MAXOP, false, true, true>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, !wrote, false, slab);
+                stream_planes<Cfg, NORM, MAXOP, false, true, true, true, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, !wrote, false, slab);
                 SINK_STAMP(7, wall_clock64());
                 wrote = true;
             }
@@ -824,7 +824,8 @@ __global__ __launch_bounds__(TT, 4) void op_sink_kernel(OpArgs a) {
                 float nrm = 0.0f;
 #pragma unroll
                 for (uint32_t z = 0; z < SINK_T; ++z) nrm += ((have >> z) & 1u) ? tn[z] : 0.0f;
-                inv = 1.0f / norm_divisor(nrm, s.norm_mode, s.eps);
+                if constexpr (RAW) { if (inside && cb == 0) f.norm_out[(size_t)p.n * hw + (size_t)oy * s.W + ox] = nrm; }
+                else inv = 1.0f / norm_divisor(nrm, s.norm_mode, s.eps);
             }
             float *o = f.out + ((size_t)p.n * s.Cs + cb) * hw + (size_t)oy * s.W + ox;
             auto add_up = [&](auto ns_tag, auto rc_tag) {
@@ -866,6 +867,19 @@ __global__ __launch_bounds__(TT, 4) void op_sink_kernel(OpArgs a) {
     }
     // (the deferred list is emptied by the next call's scan_box_kernel: the scan front end has no prebinned form)
 }
+
+// The kernels: the bodies above as they always were, and their RAW forms for one direction of the training step's blend (blend.hip:
+// weighted un-normalised sums + the raw normaliser plane).
+template <bool NORM, bool MAXOP, bool PASSES>
+__global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_kernel(OpArgs a) { op_rows_body<NORM, MAXOP, PASSES, false>(a); }
+template <bool NORM, bool MAXOP>
+__global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_kernel(OpArgs a) { op_scan_body<NORM, MAXOP, false>(a); }
+template <bool NORM, bool MAXOP>
+__global__ __launch_bounds__(TT, 4) void op_sink_kernel(OpArgs a) { op_sink_body<NORM, MAXOP, false>(a); }
+template <bool PASSES>
+__global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_blend_kernel(OpArgs a) { op_rows_body<true, false, PASSES, true>(a); }
+__global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_blend_kernel(OpArgs a) { op_scan_body<true, false, true>(a); }
+__global__ __launch_bounds__(TT, 4) void op_sink_blend_kernel(OpArgs a) { op_sink_body<true, false, true>(a); }
 
 // =========================================================================== small kernels
 
@@ -996,32 +1010,36 @@ static int do_rowbin(const float *flow, OpWs &w, int N, int H, int W, bool clean
     return 0;
 }
 
-template <bool NORM, bool MAXOP>
+template <bool NORM, bool MAXOP, bool RAW>
 static int launch_rows(OpArgs &a, OpWs &w, hipStream_t st) {
     static LdsOptIn attr_main, attr_pass;
-    if (int e = lds_opt_in((const void *)op_rows_kernel<NORM, MAXOP, false>, 159 * 1024, attr_main)) return e;
-    if (int e = lds_opt_in((const void *)op_rows_kernel<NORM, MAXOP, true>, 159 * 1024, attr_pass)) return e;
+    void (*const k_main)(OpArgs) = RAW ? op_rows_blend_kernel<false> : op_rows_kernel<NORM, MAXOP, false>;
+    void (*const k_pass)(OpArgs) = RAW ? op_rows_blend_kernel<true> : op_rows_kernel<NORM, MAXOP, true>;
+    if (int e = lds_opt_in((const void *)k_main, 159 * 1024, attr_main)) return e;
+    if (int e = lds_opt_in((const void *)k_pass, 159 * 1024, attr_pass)) return e;
     a.f.rowlist[0] = w.rowlist; a.f.items = w.items; a.f.totals = w.totals; a.f.defer = w.defer; a.f.items_cap = w.L.items_cap;
     // (the grid covers the bound on the plan's items; workgroups past totals[0] exit at once: measured free)
     const uint32_t grid = ((w.L.items_cap + 8 * SLR_XCD_GROUP - 1) / (8 * SLR_XCD_GROUP)) * 8 * SLR_XCD_GROUP;
     const uint32_t groups = channel_groups(w.L.nt, a.s.C);
     if (g_ev_start) SLR_CHECK_HIP(hipEventRecord((hipEvent_t)g_ev_start, st));      // slr_splat_time_next: the dominant kernel only
-    hipLaunchKernelGGL((op_rows_kernel<NORM, MAXOP, false>), dim3(grid, groups), dim3(TT), OpCfg::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(k_main, dim3(grid, groups), dim3(TT), OpCfg::LDS_BYTES, st, a);
     if (g_ev_stop) SLR_CHECK_HIP(hipEventRecord((hipEvent_t)g_ev_stop, st));
     g_ev_start = g_ev_stop = nullptr;
     // pieces that hold more than SEG entries (none for ordinary flows; appended by their workgroups above): pass by pass, their planes
     // dealt to up to 8 workgroups each (these run after everybody else, on an empty chip)
     const uint32_t wgroups = (uint32_t)a.s.C / 8u < 1u ? 1u : (uint32_t)a.s.C / 8u > 8u ? 8u : (uint32_t)a.s.C / 8u;
-    hipLaunchKernelGGL((op_rows_kernel<NORM, MAXOP, true>), dim3(w.L.nt < OP_DEFER_WG ? w.L.nt : OP_DEFER_WG, wgroups), dim3(TT), OpPassCfg::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(k_pass, dim3(w.L.nt < OP_DEFER_WG ? w.L.nt : OP_DEFER_WG, wgroups), dim3(TT), OpPassCfg::LDS_BYTES, st, a);
     SLR_CHECK_LAUNCH();
     return 0;
 }
 
-template <bool NORM, bool MAXOP>
+template <bool NORM, bool MAXOP, bool RAW>
 static int launch_scan(OpArgs &a, OpWs &w, hipStream_t st) {
     static LdsOptIn attr, attr_s;
-    if (int e = lds_opt_in((const void *)op_scan_kernel<NORM, MAXOP>, 159 * 1024, attr)) return e;
-    if (int e = lds_opt_in((const void *)op_sink_kernel<NORM, MAXOP>, (int)ScanCfg::LDS_BYTES, attr_s)) return e;
+    void (*const k_scan)(OpArgs) = RAW ? op_scan_blend_kernel : op_scan_kernel<NORM, MAXOP>;
+    void (*const k_sink)(OpArgs) = RAW ? op_sink_blend_kernel : op_sink_kernel<NORM, MAXOP>;
+    if (int e = lds_opt_in((const void *)k_scan, 159 * 1024, attr)) return e;
+    if (int e = lds_opt_in((const void *)k_sink, (int)ScanCfg::LDS_BYTES, attr_s)) return e;
     a.f.box = (const SrcBox *)w.box; a.f.totals = w.totals; a.f.defer = w.defer;
     a.sink_cnt = w.sink_cnt; a.sink_pool = w.sink_pool; a.sink_ent = w.sink_ent; a.sink_ent_cap = w.L.sink_ent_cap;
     // the sink launch's shape: pieces x channel groups x task slots; slabs: rows x 2 KiB per task slot, the emergency slabs of the sink_x piece
@@ -1041,21 +1059,21 @@ static int launch_scan(OpArgs &a, OpWs &w, hipStream_t st) {
     hipLaunchKernelGGL(scan_box_kernel, dim3(w.L.nt), dim3(TILE_PIX), 0, st, a.f.flow[0], (SrcBox *)w.box, a.s.H, a.s.W, w.L.tiles_x, w.L.tiles, w.totals);
     const uint32_t grid = ((w.L.nt + 8 * SLR_XCD_GROUP - 1) / (8 * SLR_XCD_GROUP)) * 8 * SLR_XCD_GROUP;
     if (g_ev_start) SLR_CHECK_HIP(hipEventRecord((hipEvent_t)g_ev_start, st));
-    hipLaunchKernelGGL((op_scan_kernel<NORM, MAXOP>), dim3(grid, groups, pieces), dim3(TT), ScanCfg::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(k_scan, dim3(grid, groups, pieces), dim3(TT), ScanCfg::LDS_BYTES, st, a);
     if (g_ev_stop) SLR_CHECK_HIP(hipEventRecord((hipEvent_t)g_ev_stop, st));
     g_ev_start = g_ev_stop = nullptr;
     // pieces of more than SEG entries (appended by their workgroups): the sink launch -- every piece by up to SINK_T x channel groups
     // workgroups at once (an empty launch: every workgroup does one scalar load and ends -- 256 or 4096 of them cost the same 2 - 3 us)
     a.sink_x = sink_x; a.sink_groups = wgroups;
     const uint32_t sink_all = sink_x * wgroups * SINK_T;
-    hipLaunchKernelGGL((op_sink_kernel<NORM, MAXOP>), dim3(sink_all < (uint32_t)SLR_SINK_GRID ? sink_all : (uint32_t)SLR_SINK_GRID), dim3(TT), ScanCfg::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(k_sink, dim3(sink_all < (uint32_t)SLR_SINK_GRID ? sink_all : (uint32_t)SLR_SINK_GRID), dim3(TT), ScanCfg::LDS_BYTES, st, a);
     SLR_CHECK_LAUNCH();
     return 0;
 }
 
 // One call of the operator: front end by grid size / flags, then the tile kernel(s) -- once per plane group (plane_group: one group unless
 // the sample's plane stack reaches 2 GiB).
-template <bool NORM, bool MAXOP>
+template <bool NORM, bool MAXOP, bool RAW = false>
 static int do_op(OpArgs &a, int ws_flags, void *ws, size_t ws_bytes, hipStream_t st, const char *who) {
     OpWs w;
     if (int e = op_ws_open(w, a.s.N, a.s.H, a.s.W, ws, ws_bytes, who)) return e;
@@ -1075,9 +1093,24 @@ static int do_op(OpArgs &a, int ws_flags, void *ws, size_t ws_bytes, hipStream_t
     for (int pb = 0; pb < C; pb += gp) {
         a.s.in = in + (size_t)pb * hw; a.f.out = out + (size_t)pb * hw;
         a.s.C = C - pb < gp ? C - pb : gp;
-        if (int e = fe == 1 ? launch_scan<NORM, MAXOP>(a, w, st) : launch_rows<NORM, MAXOP>(a, w, st)) return e;
+        if (int e = fe == 1 ? launch_scan<NORM, MAXOP, RAW>(a, w, st) : launch_rows<NORM, MAXOP, RAW>(a, w, st)) return e;
     }
     return 0;
+}
+
+// One direction of the training step's blend (blend.hip): sum[n,c] = splat(values w), norm[n] = splat(w) with
+// w = exp(clamp(logits - zmax[0], lo, hi)) * (second ? 1 - alpha[n] : alpha[n]) applied where the softmax mode applies exp(metric) --
+// the RAW instantiations of the tile kernels: raw sums, the raw normaliser plane, every element of both written.
+int splat_weighted_sum(const float *values, const float *logits, const float *zmax, const float *alpha, int second, float lo, float hi,
+                       const float *flow, float *sum, float *norm, int N, int C, int H, int W, void *ws, size_t ws_bytes, int ws_flags,
+                       hipStream_t st) {
+    if (int e = op_check_dims(N, C, H, W, __func__)) return e;
+    OpArgs a = {};
+    a.s.in = values; a.s.mul = logits; a.s.mulmax = zmax; a.f.flow[0] = flow; a.f.out = sum; a.f.norm_out = norm;
+    a.s.N = N; a.s.C = C; a.s.H = H; a.s.W = W;
+    a.s.mulmode = !logits ? MUL_ONE : zmax ? MUL_EXP_SHIFT : MUL_EXP;
+    a.s.alpha = alpha; a.s.second = second; a.s.clamp_lo = lo; a.s.clamp_hi = hi;
+    return do_op<true, false, true>(a, ws_flags, ws, ws_bytes, st, __func__);
 }
 
 }  // namespace slr

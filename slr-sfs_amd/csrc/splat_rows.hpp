@@ -222,7 +222,7 @@ __device__ __forceinline__ rsrc_t sample_planes(const TileShared &s, const Piece
 
 // A piece in ONE pass (the main kernels: no loop over work): lists -> entries -> records -> planes [cb, ce).  Returns false, with
 // nothing written, when the piece turns out to hold more than SEG entries (the pass-by-pass launch takes it).
-template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2>
+template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false>
 __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileFrame &f, const TileLds<Cfg> &L, const Piece &p, int tid,
                                                 const TileScalars &k, int cb, int ce) {
     T_STAMP(s, 0);
@@ -246,10 +246,10 @@ __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileF
     const rsrc_t rin = sample_planes(s, p, k.hw4);
     EntryRegs<Cfg> e;
     float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-    build_records<Cfg, NORM || (Cfg::NDIR > 1), G2>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+    build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
     T_STAMP(s, 6);
     PixelSums sums = {0.0f, 0.0f, 0.0f};
-    stream_planes<Cfg, NORM, MAXOP, G2, false>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
+    stream_planes<Cfg, NORM, MAXOP, G2, false, false, false, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
     T_STAMP(s, 59);
     return true;
 }
@@ -257,7 +257,7 @@ __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileF
 // A piece pass by pass (more than SEG entries: an octant that is a sink by itself; any pathological flow): a count pass gives every
 // wave its first ordinal, pass si stages the entries with ordinals [si * SEG, (si + 1) * SEG); every work-item accumulates its output
 // pixel through its own earlier stores and normalises in the last pass.
-template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2>
+template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false>
 __device__ __forceinline__ void rows_piece_passes(const TileShared &s, const TileFrame &f, const TileLds<Cfg> &L, const Piece &p, int tid,
                                                   const TileScalars &k, int cb, int ce) {
     rows_setup<Cfg, SORTED>(f, L, p, tid);
@@ -275,9 +275,9 @@ __device__ __forceinline__ void rows_piece_passes(const TileShared &s, const Til
         __syncthreads();
         EntryRegs<Cfg> e;
         float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-        build_records<Cfg, NORM || (Cfg::NDIR > 1), G2>(s, L, p, tid, min((uint32_t)Cfg::SEG, all - lo), rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1,
+        build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW>(s, L, p, tid, min((uint32_t)Cfg::SEG, all - lo), rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1,
                                                          e, preA, preB);
-        stream_planes<Cfg, NORM, MAXOP, G2, true>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, si == 0, si + 1 == npass);
+        stream_planes<Cfg, NORM, MAXOP, G2, true, false, false, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, si == 0, si + 1 == npass);
     }
     __syncthreads();
 }

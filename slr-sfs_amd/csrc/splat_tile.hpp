@@ -63,6 +63,11 @@ struct TileShared {                // the same for every frame of a launch
     int mulmode, mulmode2, norm_mode;
     float eps, init;               // normaliser clamp; start value of the maximum splat
     long long *trace;              // development builds (-DSLR_TRACE): 64 time stamps per workgroup, or nullptr
+    // RAW instantiations only (one direction of the training step's blend, blend.hip): the weight of a source pixel of sample n is
+    // exp(clamp(mul - mulmax[0], clamp_lo, clamp_hi)) * a, a = alpha[n] or 1 - alpha[n] (second); no logits (mulmode MUL_ONE): a
+    const float *alpha;            // [N] on the device
+    float clamp_lo, clamp_hi;
+    int second;
 };
 struct SrcBox { int x0, x1, y0, y1; };             // scan front end: inclusive range of a source tile's footprint NW corners; x0 > x1: none
 struct TileFrame {
@@ -186,7 +191,8 @@ __device__ __forceinline__ void prefetch_planes(rsrc_t rin, const EntryRegs<Cfg>
 // WEIGHTED: the record weights carry m (normalised / fused kernels); else m is not applied (plain summation, maximum splat: the
 // pure bilinear weights).  G2 (a second weight group shares the records): the records keep the PURE bilinear weights, m multiplies
 // the first group's values when they are staged, and the entry's slot of a special chunk carries  m | in2 * m2 | m2.
-template <class Cfg, bool WEIGHTED, bool G2>
+// RAW (with WEIGHTED): the blend weight of TileShared.alpha / clamp_lo / clamp_hi / second instead of mulmode's.
+template <class Cfg, bool WEIGHTED, bool G2, bool RAW = false>
 __device__ __forceinline__ void build_records(const TileShared &s, const TileLds<Cfg> &L, const Piece &p, int tid, uint32_t total,
                                               rsrc_t rin, uint32_t hw4, int c0, int cmax, float shift, float sc0, float sc1,
                                               EntryRegs<Cfg> &e, float (&preA)[Cfg::EPT][4], float (&preB)[Cfg::EPT][4]) {
@@ -223,7 +229,11 @@ __device__ __forceinline__ void build_records(const TileShared &s, const TileLds
         //  become a vector memory load behind the plane loads)
         const float sc = (Cfg::NDIR > 1 && dir[j]) ? sc1 : sc0;
         float m = sc;
-        if (WEIGHTED) {
+        if constexpr (RAW) {
+            const float al = s.alpha[p.n];
+            m = s.second ? 1.0f - al : al;
+            if (s.mulmode != MUL_ONE) m = expf(fminf(fmaxf(mm[j] - shift, s.clamp_lo), s.clamp_hi)) * m;
+        } else if (WEIGHTED) {
             if (s.mulmode == MUL_PLANE) m = mm[j] * m;
             else if (s.mulmode >= MUL_EXP) m = expf(mm[j] - shift) * m;
         }
@@ -574,7 +584,8 @@ struct PixelSums { float nrm, g2_sum, g2_nrm; };
 // batch -- other workgroups the rest -- so it accumulates its un-normalised sums in a slab of its own ([planes of its channel group + a
 // normaliser row][8 x 64 pixels of the tile], through its own earlier stores) and the piece's last workgroup adds the slabs up.
 // ADAPT: the per-wave choice of how long a list a lane walks alone (pixel_list) and 4 records per lane and trip in the cooperative walks.
-template <class Cfg, bool NORM, bool MAXOP, bool G2, bool ACCUM, bool SLAB = false, bool ADAPT = SLAB>
+// RAW (with NORM): the sums leave un-normalised and the normaliser goes to f.norm_out as it is (the caller adds two directions up).
+template <class Cfg, bool NORM, bool MAXOP, bool G2, bool ACCUM, bool SLAB = false, bool ADAPT = SLAB, bool RAW = false>
 __device__ __forceinline__ void stream_planes(const TileShared &s, const TileFrame &f, const TileLds<Cfg> &L, const Piece &p, int tid,
                                               rsrc_t rin, uint32_t hw4, int cb, int ce, const EntryRegs<Cfg> &e,
                                               float (&preA)[Cfg::EPT][4], float (&preB)[Cfg::EPT][4], PixelSums &sums, bool first, bool last,
@@ -623,6 +634,8 @@ __device__ __forceinline__ void stream_planes(const TileShared &s, const TileFra
         }
         if constexpr (SLAB) {
             buf_st<BUF_SC1>(rout, voff, (uint32_t)(ce - cb) * obytes, sums.nrm);    // the normaliser so far: the slab's last row
+        } else if constexpr (RAW) {
+            if (last && inside && cb == 0) f.norm_out[(size_t)p.n * hw + opix] = sums.nrm;
         } else {
             if (last && inside && f.norm_out && cb == 0) f.norm_out[(size_t)p.n * hw + opix] = norm_divisor(sums.nrm, s.norm_mode, s.eps);
             inv = 1.0f / norm_divisor(sums.nrm, s.norm_mode, s.eps);       // ONE division per output pixel
@@ -692,7 +705,7 @@ __device__ __forceinline__ void stream_planes(const TileShared &s, const TileFra
                 const uint32_t soff = (uint32_t)(c0 + u - cbase) * obytes;
                 float r = acc[u];
                 if (ACCUM && !first) { const float o = buf_ld(rout, voff, soff); r = MAXOP ? fmaxf(r, o) : r + o; }   // earlier passes of this piece
-                if (NORM && !SLAB && (!ACCUM || last)) r *= inv;
+                if (NORM && !SLAB && !RAW && (!ACCUM || last)) r *= inv;
                 buf_st<SLAB ? BUF_SC1 : SLR_STORE_AUX>(rout, voff, soff, r);      // (a slab is read by another workgroup)
             }
         }
