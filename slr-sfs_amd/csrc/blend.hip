@@ -18,7 +18,10 @@
 //   blend_max_fix_kernel   one workgroup per direction: the partial sums in a fixed order, subtracted at the element that holds the
 //                          maximum (the first one in memory order: ties are not split as torch splits them).
 // No float atomics anywhere: every result is the same from run to run given the same forward result.
+// A source pixel's footprint (`Foot`) and the corner sums of one channel (`corner_sum`, `disp_grad_add`) are those of grad.hip, in
+// splat_gather.hpp; the gather passes the weights multiplied by the corners' inverse normaliser.
 #include "splat_core.hpp"
+#include "splat_gather.hpp"
 
 namespace slr {
 
@@ -98,35 +101,7 @@ __global__ __launch_bounds__(256) void blend_prepass_kernel(BlendArgs a) {
     ax[HW] = nrm >= a.eps ? -(s * inv) : 0.0f;
 }
 
-// What a source pixel knows about its four corners: in-image flags, the offsets it reads (an out-of-image corner reads the pixel itself
-// and its product is replaced by +0.0, as in grad_kernel), the weights and their derivatives (softsplat.py:289-299).
-struct BlendFoot {
-    bool ok, k[4];
-    int o[4];
-    float w[4], dx[4], dy[4];
-};
-
-__device__ __forceinline__ BlendFoot blend_foot(const float *f, int i, int x, int y, int H, int W) {
-    const int HW = H * W;
-    const float fx = f[i], fy = f[HW + i];
-    const Corners c = make_corners(fx, fy, x, y);
-    BlendFoot t;
-    t.ok = c.ok;
-    t.k[0] = c.ok & in_image(c.x0, c.y0, H, W); t.k[1] = c.ok & in_image(c.x0 + 1, c.y0, H, W);
-    t.k[2] = c.ok & in_image(c.x0, c.y0 + 1, H, W); t.k[3] = c.ok & in_image(c.x0 + 1, c.y0 + 1, H, W);
-    const int o = c.y0 * W + c.x0;
-    t.o[0] = t.k[0] ? o : i; t.o[1] = t.k[1] ? o + 1 : i; t.o[2] = t.k[2] ? o + W : i; t.o[3] = t.k[3] ? o + W + 1 : i;
-    const float X = (float)x + fx, Y = (float)y + fy;
-    const float ax = (float)(c.x0 + 1) - X, bx = X - (float)c.x0;
-    const float ay = (float)(c.y0 + 1) - Y, by = Y - (float)c.y0;
-    t.w[0] = c.w[0]; t.w[1] = c.w[1]; t.w[2] = c.w[2]; t.w[3] = c.w[3];
-    t.dx[0] = -ay; t.dx[1] = ay; t.dx[2] = -by; t.dx[3] = by;
-    t.dy[0] = -ax; t.dy[1] = -bx; t.dy[2] = ax; t.dy[3] = bx;
-    return t;
-}
-
 // GV: some direction wants dV; GH: some direction wants dZ or dD (the partial sums).  grid (HW / 256, 2N, groups).
-#define SLR_BLEND_U 4
 template <bool GV, bool GH>
 __global__ __launch_bounds__(256) void blend_gather_kernel(BlendArgs a) {
     constexpr int U = SLR_BLEND_U;
@@ -139,7 +114,8 @@ __global__ __launch_bounds__(256) void blend_gather_kernel(BlendArgs a) {
     if (i >= HW) return;
     const int gz = blockIdx.z, cb = gz * a.cper, C = min(a.cper, a.C - cb);
     const int y = i / W, x = i - y * W;
-    const BlendFoot t = blend_foot(D.d + (size_t)n * 2 * HW, i, x, y, H, W);
+    const float *f = D.d + (size_t)n * 2 * HW;
+    const Foot t(f[i], f[HW + i], x, y, i, H, W);
     // A_c(q_k) = G_c(q_k) * inv(q_k): the inverse normaliser joins the corner's weight and its derivatives once
     const float *ax = a.aux + (size_t)n * 2 * HW;
     float bw[4], bdx[4], bdy[4];
@@ -160,29 +136,22 @@ __global__ __launch_bounds__(256) void blend_gather_kernel(BlendArgs a) {
     float h = 0.0f, gx = 0.0f, gy = 0.0f;
     // U channels per pass, all their loads issued before the first use; channels past C in the last pass re-read channel C - 1
     for (int ch = 0; ch < C; ch += U) {
-        float a0[U], a1[U], a2[U], a3[U], v[U];
+        float g4[U][4], v[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t po = (size_t)min(ch + u, C - 1) * HW;
-            a0[u] = gp[po + t.o[0]]; a1[u] = gp[po + t.o[1]]; a2[u] = gp[po + t.o[2]]; a3[u] = gp[po + t.o[3]];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g4[u][q] = gp[po + t.o[q]];
             if (GH) v[u] = vp[po];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (ch + u >= C) continue;
-            float g = 0.0f;
-            g += t.k[0] ? a0[u] * bw[0] : 0.0f;
-            g += t.k[1] ? a1[u] * bw[1] : 0.0f;
-            g += t.k[2] ? a2[u] * bw[2] : 0.0f;
-            g += t.k[3] ? a3[u] * bw[3] : 0.0f;
+            const float g = corner_sum(t.k, g4[u], bw);
             if (GV && want_v) op[(size_t)(ch + u) * HW] = t.ok ? w * g : 0.0f;
             if (GH) {
                 h += v[u] * g;
-                const float t0 = v[u] * a0[u], t1 = v[u] * a1[u], t2 = v[u] * a2[u], t3 = v[u] * a3[u];
-                gx += t.k[0] ? t0 * bdx[0] : 0.0f; gy += t.k[0] ? t0 * bdy[0] : 0.0f;
-                gx += t.k[1] ? t1 * bdx[1] : 0.0f; gy += t.k[1] ? t1 * bdy[1] : 0.0f;
-                gx += t.k[2] ? t2 * bdx[2] : 0.0f; gy += t.k[2] ? t2 * bdy[2] : 0.0f;
-                gx += t.k[3] ? t3 * bdx[3] : 0.0f; gy += t.k[3] ? t3 * bdy[3] : 0.0f;
+                disp_grad_add(gx, gy, t.k, v[u], g4[u], bdx, bdy);
             }
         }
     }
@@ -208,16 +177,13 @@ __global__ __launch_bounds__(256) void blend_finish_kernel(BlendArgs a) {
         h += pp[0]; gx += pp[HW]; gy += pp[2 * (size_t)HW];
     }
     const int y = i / W, x = i - y * W;
-    const BlendFoot t = blend_foot(D.d + (size_t)n * 2 * HW, i, x, y, H, W);
+    const float *f = D.d + (size_t)n * 2 * HW;
+    const Foot t(f[i], f[HW + i], x, y, i, H, W);
     const float *rp = a.aux + (size_t)n * 2 * HW + HW;
-    float r = 0.0f, rx = 0.0f, ry = 0.0f;
+    float rv[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float rv = rp[t.o[k]];
-        r += t.k[k] ? rv * t.w[k] : 0.0f;
-        rx += t.k[k] ? rv * t.dx[k] : 0.0f;
-        ry += t.k[k] ? rv * t.dy[k] : 0.0f;
-    }
+    for (int k = 0; k < 4; ++k) rv[k] = rp[t.o[k]];
+    const float r = corner_sum(t.k, rv, t.w), rx = corner_sum(t.k, rv, t.dx), ry = corner_sum(t.k, rv, t.dy);
     bool pass;
     const float al = a.alpha[n];
     const size_t zi = (size_t)n * HW + i;
@@ -275,15 +241,13 @@ static int blend_groups(int N, int C, int H, int W) {
     g = g > byc ? byc : g;
     return g < 1 ? 1 : (int)g;
 }
-static int blend_cper(int C, int groups) { return groups > 1 ? ((C + groups - 1) / groups + SLR_BLEND_U - 1) / SLR_BLEND_U * SLR_BLEND_U : C; }
 
 struct BlendLayout { size_t stack, plane, aux, part, bsum, idx, fwd, bwd; int groups, cper, blocks; };
 static BlendLayout blend_layout(int N, int C, int H, int W) {
     BlendLayout L;
     const size_t hw = (size_t)H * W;
-    L.groups = blend_groups(N, C, H, W);
-    L.cper = blend_cper(C, L.groups);
-    L.groups = (C + L.cper - 1) / L.cper;
+    const ChannelSplit cs = split_channels(C, blend_groups(N, C, H, W), SLR_BLEND_U);
+    L.groups = cs.groups; L.cper = cs.cper;
     L.blocks = (int)((hw + 255) / 256);
     L.stack = al256((size_t)N * C * hw * 4);                       // the raw sums of one direction ...
     L.plane = al256((size_t)N * hw * 4);                           // ... and its raw normaliser
@@ -365,9 +329,7 @@ SLR_EXPORT int slr_splat_blend_backward(const float *values_f, const float *logi
     a.N = N; a.C = C; a.H = H; a.W = W; a.cper = L.cper; a.groups = L.groups;
     const dim3 g1(L.blocks, N), g2(L.blocks, 2 * N), g3(L.blocks, 2 * N, L.groups);
     hipLaunchKernelGGL(blend_prepass_kernel, g1, dim3(256), 0, st, a);
-    if (gv && gh) hipLaunchKernelGGL((blend_gather_kernel<true, true>), g3, dim3(256), 0, st, a);
-    else if (gv) hipLaunchKernelGGL((blend_gather_kernel<true, false>), g3, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((blend_gather_kernel<false, true>), g3, dim3(256), 0, st, a);
+    dispatch_bools(gv, gh, [&](auto v, auto h) { hipLaunchKernelGGL((blend_gather_kernel<decltype(v)::value, decltype(h)::value>), g3, dim3(256), 0, st, a); });
     if (gh) {
         hipLaunchKernelGGL(blend_finish_kernel, g2, dim3(256), 0, st, a);
         if ((grad_logits_f && a.dir[0].zmax) || (grad_logits_p && a.dir[1].zmax))

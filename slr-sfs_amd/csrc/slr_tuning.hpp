@@ -63,7 +63,24 @@
 #define SLR_ROWS_GROUP 2        // narrow pieces: 0 one lane per output pixel; 1 groups of 8 / 4 lanes up to 16 columns; 2 also pairs up to 32 columns
 #define SLR_FRONT_END -1        // default of slr_splat_set_front_end: -1 = by grid size, 0 bins, 1 scan (boxes), 2 rows
 
-#define SLR_CONV_SKIP_FILL 3     // 3x3 kernels with the block's 1x1 skip inside (conv.hip, SKIP): skip chunks staged per barrier pair (16 KiB of LDS and 16 registers in flight each)
+// ---- backward (grad.hip: grad_kernel, grad_tile_kernel; blend.hip: blend_gather_kernel).  us = both gradients in one launch, 65 x 768 x 1280,
+// identity / Euler t=30 / t=59 (tools/bwdbench.py) unless said otherwise
+#define SLR_GRAD_U 4            // grad_kernel: channels per pass, all their loads issued before the first use
+#define SLR_BLEND_U 4           // blend_gather_kernel: the same
+#define SLR_GRAD_TU 4           // grad_tile_kernel: channels per pass.  Round 3, 4 / 8 / 16 at box 2048 / 1536 / 1024: t=30 223 / 245 / 301 us (grad_kernel: 279)
+#define SLR_GRAD_BOX 4096       // floats of LDS per channel (e.g. 32 rows x 128 columns); x TU channels x 4 bytes = 64 KiB: two workgroups per CU.  Round 4:
+                                // 2048: 169 / 201 / 290, 3072: 169 / 196 / 271, 4096: 165-171 / 190-197 / 248-255, 5120 (40 staging registers): 184 / 253 / 279;
+                                // 2 channels per pass at 4096 / 6144 / 8192 / 10240: 170 / 189 / 274, 172 / 213 / 258, 171 / 253 / 273, 213 / 365 / 368
+#define SLR_GRAD_BENT 2         // stage through LDS only where a wave's destinations spread over more rows than this (1 and 3: within 2 %)
+#define SLR_GRAD_STRIPS 2       // column strips of a block with a destination box each (power of two).  Round 5, 1 -> 2: t=30 190-197 -> 188-192, t=59 248-258 ->
+                                // 243-251; 4: the bookkeeping eats the gain
+#define SLR_GRAD_WAVES 4        // __launch_bounds__ waves per SIMD of the tiled kernel (<= 128 VGPRs; its box allows two workgroups per CU anyway; 6: measured, not kept)
+#define SLR_GRAD_SLOTS 1024     // small grids: channel groups while the launch stays within this many workgroups (two rounds of the 512 slots) ...
+#define SLR_GRAD_GROUPS_MAX 4   // ... at most this many ([2,65,256,256] t=30: 81.5 -> 52 us) ...
+#define SLR_GRAD_GROUPS_MIN 2   // ... and on grids larger than the chip this many: two groups (group-major launch order) halve the life of the blocks a flow's
+                                // sinks make slow.  Round 6, 1 / 2 / 4 groups: 176 / 187 / 230, 167 / 186 / 210, 189 / 203 / 215
+
+#define SLR_CONV_SKIP_FILL 3    // 3x3 kernels with the block's 1x1 skip inside (conv.hip, SKIP): skip chunks staged per barrier pair (16 KiB of LDS and 16 registers in flight each)
 
 #define SLR_CONV_DEEP_STAGE 1    // 3x3 split kernels with fewer than 8 rows per wave: staging loads five taps ahead of their use (three register sets) instead of two
 

@@ -261,6 +261,38 @@ def test_device_code_has_only_the_safe_packed_fp32_form(tmp_path):
     assert mfma > 0                          # the disassembly really is the convolution's device code too
 
 
+def test_block_rule_constants_of_splat_f64_are_the_shipped_ones():
+    """tests/splat_f64.py restates the block rule of grad_tile_kernel so that tests can assert which of its paths a flow reaches; the
+    numbers it restates are the values that ship: the SLR_GRAD_* of csrc/slr_tuning.hpp, the tile of csrc/slr_common.hpp and the
+    workgroup of csrc/grad.hip (one work-item per pixel of a tile)."""
+    import splat_f64 as F64
+    csrc = os.path.join(ROOT, "slr-sfs_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+    tuning, common, grad = read("slr_tuning.hpp"), read("slr_common.hpp"), read("grad.hip")
+
+    def shipped(name):
+        found = re.findall(rf"^\s*#\s*define\s+{name}\s+(\d+)\b", tuning, re.M)
+        assert len(found) == 1, (name, found)
+        return int(found[0])
+
+    def defined_as(text, name, value):
+        """`constexpr int NAME = VALUE;` whatever the spacing; VALUE None: the integer it is set to"""
+        want = r"[0-9]+" if value is None else value
+        m = re.search(rf"constexpr\s+int\s+{name}\s*=\s*({want})\s*;", text)
+        assert m, f"constexpr int {name} = {want}; not found"
+        return m.group(1)
+
+    defined_as(common, "TILE_H", "SLR_TILE_H")
+    defined_as(common, "TILE_PIX", r"TILE_W\s*\*\s*TILE_H")
+    defined_as(grad, "GT_THREADS", "TILE_PIX")
+    defined_as(grad, "GT_BOX", "SLR_GRAD_BOX")
+    assert not re.search(r"#\s*define\s+SLR_GRAD_", grad)      # a constant defined there again would shadow the shipped one
+    tile_w = int(defined_as(common, "TILE_W", None))
+    assert (F64.TILE_H, F64.TILE_W) == (shipped("SLR_TILE_H"), tile_w)
+    assert (F64.STRIPS, F64.BOX, F64.BENT) == (shipped("SLR_GRAD_STRIPS"), shipped("SLR_GRAD_BOX"), shipped("SLR_GRAD_BENT"))
+    assert F64.THREADS == F64.TILE_H * F64.TILE_W
+
+
 def test_synthesize_refuses_grids_that_are_not_multiples_of_8():
     from slr_sfs_amd import pipeline
     an = pipeline.BaselineAnimator()
