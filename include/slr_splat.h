@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 13
+#define SLR_ABI_VERSION 14
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -570,6 +570,39 @@ int slr_relu_maxpool2x2_b8(const float *in, float *out, int N, int C, int H, int
 size_t slr_feature_cos_ws_bytes(int N, int H, int W);
 int slr_feature_cos_distance(const float *f0, const float *f1, float *out, int N, int C, int H, int W, void *ws, size_t ws_bytes,
                              void *stream);
+
+/* ------------------------------------------------------------------ training loss (ABI 14; csrc/loss.hip)
+ * The generator loss of the reference, models/losses/synthesis.py:61-109 (SynthesisLoss, --losses 1.0_l1 10.0_content): nn.L1Loss and the
+ * VGG19 PerceptualLoss (:166-185; models/networks/architectures.py:82-115), each with its gradient to the predicted image.  The VGG19 is
+ * frozen: its 13 convolutions run on slr_conv3x3_forward with SLR_CONV_F32 and channel-blocked features, and so do their backward-data
+ * convolutions (3x3 / stride 1 / pad 1: the same convolution with the weights flipped and transposed).  The entry points below are the
+ * device code around them.  None synchronises; sums are deterministic (per-workgroup partial sums in double, added in a fixed order by a
+ * second launch -- no atomics).  `gscale` is a DEVICE scalar: the gradient arriving at the loss value (autograd's grad_output). */
+
+/* Partial sums of slr_l1_loss_grad / slr_feature_l1_gate_b8 for a tensor of N*C*H*W elements. */
+size_t slr_loss_ws_bytes(int N, int C, int H, int W);
+
+/* nn.L1Loss() (synthesis.py:134-140): loss[0] = mean |pred - gt| over all elements of [N,C,H,W] (any count, any 4-byte alignment);
+ * with grad: grad = sign(pred - gt) * (coef * gscale[0]), sign(0) = 0, the product formed in fp32 in that order (coef = 1 / count for
+ * the mean).  loss or grad may be NULL (not both); ws (slr_loss_ws_bytes, 8-byte aligned) is needed with loss. */
+int slr_l1_loss_grad(const float *pred, const float *gt, float *loss, float *grad, float coef, const float *gscale,
+                     int N, int C, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* One pass over a VGG19 slice's features (PerceptualLoss.forward, synthesis.py:176-185: criterion(pred_fs[i], gt_fs[i]) and its backward,
+ * with the nn.ReLU in front of it): a, b raw (pre-ReLU) features of prediction / ground truth, g_in the gradient arriving at relu(a)
+ * from the layers above, all [N,C,H,W] channel-blocked, C % 8 == 0, 16-byte aligned.
+ *   sum[0] = sum |relu(a) - relu(b)|                                           (needs b and ws; the caller divides by the count)
+ *   g_out  = a > 0 ? g_in + sign(relu(a) - relu(b)) * (coef * gscale[0]) : 0   (g_in = NULL counts as 0)
+ *   b = NULL: g_out = a > 0 ? g_in : 0, the ReLU backward of a layer that ends no slice.
+ * sum or g_out may be NULL (not both).  fp32 operations in the order written: bit-equal to the same expression in torch. */
+int slr_feature_l1_gate_b8(const float *a, const float *b, const float *g_in, float *sum, float *g_out, float coef,
+                           const float *gscale, int N, int C, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* Backward of slr_relu_maxpool2x2_b8 (nn.ReLU + nn.MaxPool2d(2, 2) of torchvision's vgg19.features): x [N,C,H,W] the raw activation,
+ * g [N,C,H/2,W/2] the pooled gradient, out [N,C,H,W], all channel-blocked.  g goes to the first maximum of its window in row-major
+ * order (torch's choice) if that maximum is > 0; every other element, the last row / column of an odd H / W included, gets 0.
+ * Every element of out is written exactly once. */
+int slr_relu_maxpool2x2_backward_b8(const float *x, const float *g, float *out, int N, int C, int H, int W, void *stream);
 
 #ifdef __cplusplus
 }

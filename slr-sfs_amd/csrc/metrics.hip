@@ -8,36 +8,9 @@
 // Every reduction is deterministic: per-workgroup partial sums in double, written to a caller-owned workspace and added by a second
 // launch in a fixed order -- no atomics, and an image's result depends on that image only (not on its batch or its position in it).
 #include "slr_common.hpp"
+#include "slr_reduce.hpp"
 
 namespace slr {
-
-// ------------------------------------------------------------------ shared: deterministic reductions
-// Sum of v over the 64 lanes of a wave: a butterfly, the same order on every lane and every run.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum over a workgroup of NW waves of K values per thread; thread 0 returns the sums, added in wave order.  Every thread calls it.
-template <int K, int NW>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[NW]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[k][wave] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += red[k][w];
-            v[k] = s;
-        }
-}
 
 // ------------------------------------------------------------------ SSIM + squared error
 // models/losses/ssim.py:_ssim with the window of create_window (1-D Gaussian, sigma 1.5, normalised, 2-D = outer product) and
