@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 14
+#define SLR_ABI_VERSION 15
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -603,6 +603,37 @@ int slr_feature_l1_gate_b8(const float *a, const float *b, const float *g_in, fl
  * order (torch's choice) if that maximum is > 0; every other element, the last row / column of an odd H / W included, gets 0.
  * Every element of out is written exactly once. */
 int slr_relu_maxpool2x2_backward_b8(const float *x, const float *g, float *out, int N, int C, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------ trainable 3x3 convolutions (ABI 15; csrc/conv_grad.hip)
+ * What torch autograd computes for the learning 3x3 / stride 1 / pad 1 convolutions of the reference's decoder: nn.Conv2d
+ * (models/layers/blocks.py:66-87) and PartialConv2d (models/layers/partialconv2d.py:61-74).  The gradient to the input is the forward
+ * kernel with flipped, transposed weights (SLR_CONV_F32); the entry points below are the rest.  None synchronises, none uses atomics:
+ * the same inputs and the same split count give the same bits from run to run. */
+#define SLR_GRAD_X_B8 1        /* `x` is channel-blocked, [N,Cin/8,H,W,8] (Cin % 8 == 0, 16-byte aligned) */
+#define SLR_GRAD_G_B8 2        /* `g` (and `gr`) is channel-blocked, [N,C/8,H,W,8] (C % 8 == 0, 16-byte aligned) */
+
+/* Workspace of the two calls below, in bytes:
+ *   al256(N * Cout * ceil(H * W / 256) * 8)          the bias gradient's partial sums (double)
+ * + al256(S * 9 * Cout * Cin * 4)                    the weight gradient's partial sums of S slabs (float); nothing for Cin = 0
+ * S = min(splits, chunks) for splits > 0; for splits = 0 the library's choice min(ceil(512 / channel tiles), chunks, 32 MiB / (36 Cout Cin))
+ * with chunks = N * ceil(H / 2) * ceil(W / 32) and channel tiles = ceil(Cin / 64) * ceil(Cout / 64) (csrc/slr_tuning.hpp): at most
+ * 32 MiB + the bias part.  Cin = 0: the bias part alone, what the scale / bias pass needs.  0 for sizes the calls refuse. */
+size_t slr_conv3x3_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int splits);
+
+/* Weight and bias gradient of out = conv3x3(x, w) + b (what autograd's backward of F.conv2d, blocks.py:66-87, returns for weight and bias):
+ *   dw[co][ci][ky][kx] = sum_{n,y,x} g[n,co,y,x] * x[n,ci,y+ky-1,x+kx-1] (zero padding), plain [Cout,Cin,3,3];  db[co] = sum g[n,co,y,x].
+ * x [N,Cin,H,W], g [N,Cout,H,W]; any Cin, Cout, H, W >= 1.  fp32 products and sums on v_mfma_f32_32x32x2_f32 inside a slab of pixels, the
+ * slabs added in double in a fixed order; db in double throughout.  splits: 0 = the library's choice, > 0 = that many slabs (at most one
+ * per chunk).  layout: SLR_GRAD_X_B8 | SLR_GRAD_G_B8.  db may be NULL.  ws: 256-byte aligned, else SLR_E_WORKSPACE. */
+int slr_conv3x3_weight_grad(const float *x, const float *g, float *dw, float *db, int N, int Cin, int Cout, int H, int W,
+                            int splits, int layout, void *ws, size_t ws_bytes, void *stream);
+
+/* One pass over the gradient g [N,C,H,W] arriving at a partial convolution's output (the backward of partialconv2d.py:64-74,
+ * out = (raw * ratio + b) * um):  gr = g * r with r = ratio * um [N,1,H,W] -- the gradient at raw, input of the backward-data convolution
+ * and of the weight gradient, in g's layout (SLR_GRAD_G_B8), bit-equal to the fp32 product -- and db[c] = sum g * um (um [N,1,H,W];
+ * NULL = 1: the plain convolution's bias gradient).  gr or db may be NULL (not both); gr needs r; ws is needed with db. */
+int slr_conv_grad_scale_bias(const float *g, const float *r, const float *um, float *gr, float *db, int N, int C, int H, int W,
+                             int layout, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

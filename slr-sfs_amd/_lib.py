@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 14
+ABI_VERSION = 15
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -88,6 +88,9 @@ SIGNATURES = {
     "slr_l1_loss_grad": (_i, [_fp, _fp, _fp, _fp, _f, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_feature_l1_gate_b8": (_i, [_fp, _fp, _fp, _fp, _fp, _f, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_relu_maxpool2x2_backward_b8": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "slr_conv3x3_grad_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "slr_conv3x3_weight_grad": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_conv_grad_scale_bias": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

@@ -84,6 +84,21 @@
 
 #define SLR_CONV_DEEP_STAGE 1    // 3x3 split kernels with fewer than 8 rows per wave: staging loads five taps ahead of their use (three register sets) instead of two
 
+// ---- weight gradient of the 3x3 convolution (conv_grad.hip): the reduction over the pixels is split over workgroups ("slabs")
+#define SLR_WGRAD_SLOTS 512     // workgroups of a weight-gradient launch: two per CU (one resident at a time: 144 accumulator + ~170 other registers) ...
+#define SLR_WGRAD_WS_MB 32      // ... while the slabs' partial sums ([slab][9][Cout][Cin] fp32, written once and read once) stay within this
+#ifdef __cplusplus
+// The split count the library chooses (slr_conv3x3_weight_grad with splits = 0): enough slabs to fill the slots with this layer's channel
+// tiles, at most one per chunk of pixels, at most SLR_WGRAD_WS_MB of partial sums (bytes_per_slab = Cout * Cin * 9 * 4).
+inline long long slr_wgrad_auto_splits(long long chunks, long long channel_tiles, long long bytes_per_slab) {
+    long long s = (SLR_WGRAD_SLOTS + channel_tiles - 1) / channel_tiles;
+    const long long cap = ((long long)SLR_WGRAD_WS_MB << 20) / bytes_per_slab;
+    if (s > cap) s = cap;
+    if (s > chunks) s = chunks;
+    return s < 1 ? 1 : s;
+}
+#endif
+
 // ---- development aids
 
 // ---- variant builds (csrc/Makefile: TUNE="NAME=value ...")
