@@ -347,7 +347,16 @@ int slr_pconv_epilogue(const float *raw0, const float *bias, const float *mask_b
 /* The split-f16 convolution kernels below represent an activation x as two f16 halves of x * xscale (`xscale` of the
  * forward calls: a power of two in (0, 64]; 64 = the default): exact-domain for |x| < 65472 / xscale -- 1023 at 64
  * (post-BN activations are O(1 .. 10^2)), 65472 at 1 (the low halves of values below 2^-3 are then f16 subnormals:
- * absolute error <= 2^-25 per value).  A larger activation is CLAMPED there (no inf / NaN), which makes the frame wrong
+ * absolute error <= 2^-25 per value).  The LOWER edge: the lo half is a normal f16 number only for |x| * xscale >= 2^-2; below that
+ * it is a subnormal (absolute resolution 2^-25 / xscale per value), below |x| * xscale = 2^-14 the hi half is one too and below
+ * 2^-25 the value is 0.  gfx950 keeps f16 subnormals in the conversion and in the A / B inputs of v_mfma_f32_32x32x16_f16
+ * (measured, tests/test_gpu_conv_range.py: bit-exact probes), so the error grows smoothly, 16 x per 2^-4 of input magnitude.
+ * Measured E = max|out - fp64| / max|fp64| of a layer by the standard deviation of its input (19 kernel / shape cases each):
+ *     input std        >= 2^-4    2^-8      2^-12     2^-16     2^-20        (a plain fp32 convolution: 0.9 - 3e-7 throughout)
+ *     xscale 64 (E <=)  5.9e-7    6.3e-7    1.4e-6    2.1e-5    3.5e-4
+ *     xscale 1  (E <=)  7.5e-7    4.9e-6    8.7e-5    1.4e-3    2.4e-2       (5.9e-7 at std >= 1)
+ * i.e. worse than 10 x plain fp32 below an input std of about 2^-13 at xscale 64 and about 2^-7 at xscale 1.  Nothing counts or
+ * reports this underflow: it loses precision gradually, it does not make a frame wrong.  A larger activation is CLAMPED at the upper edge (no inf / NaN), which makes the frame wrong
  * rather than inexact -- the reference's fp32 convolution has no such limit -- so every wave that had to clamp adds to
  * a counter.  The counter is ONE PER DEVICE (shared by all streams and host threads using that device).
  *   slr_conv_saturation_count: *count = the counter of the current device after everything enqueued on `stream` so far

@@ -111,7 +111,11 @@ class fp32_kernels:
 
 class activation_scale:
     """Context manager: pre-scale of the activations in the split-f16 kernels (a power of two in (0, 64]; default 64).
-    The exact domain of the split is |activation| < 65472 / scale: 1023 at 64, 65472 at 1 (csrc/conv.hip)."""
+    The exact domain of the split is |activation| < 65472 / scale: 1023 at 64, 65472 at 1 (csrc/conv.hip).
+    The lower edge (include/slr_splat.h: xscale; measured by tests/test_gpu_conv_range.py): below |activation| * scale = 2^-2 the lo half is an
+    f16 subnormal, which gfx950 keeps, so a layer's error against fp64 grows smoothly as its inputs shrink -- input std 1 / 2^-8 / 2^-16:
+    5.9e-7 / 6.3e-7 / 2.1e-5 of the output range at scale 64, 5.9e-7 / 4.9e-6 / 1.4e-3 at scale 1 (plain fp32: 0.9 - 3e-7); worse than ten
+    times plain fp32 below an input std of about 2^-13 at scale 64, 2^-7 at scale 1.  Nothing counts this underflow."""
 
     def __init__(self, scale):
         m, e = math.frexp(float(scale))
@@ -689,7 +693,9 @@ RUNG_FP32 = len(RUNG_SCALES)
 def rung_context(rung):
     """Arithmetic of the convolutions on rung ``rung`` of the "auto" ladder: 0 split-f16 at activation scale 2^6 (exact for
     |x| < 1023), 1 split-f16 at scale 1 (|x| < 65472), RUNG_FP32 the fp32 matrix instructions (fp32_kernels(winograd=False):
-    no limit; the safety net is the strict rung)."""
+    no limit; the safety net is the strict rung).  The ladder reacts to the UPPER edge only: rung 1 is 64 times coarser than rung 0 on small
+    activations (activation_scale: worse than ten times plain fp32 below an input std of about 2^-7 instead of 2^-13), "auto" does not detect
+    underflow, and an animator that once moved to rung 1 stays there for its later clips (guarded: ``owner``)."""
     return fp32_kernels(winograd=False) if rung >= RUNG_FP32 else activation_scale(RUNG_SCALES[rung])
 
 
