@@ -19,8 +19,9 @@
 //   * after the last chunk the two halves of the positions meet through LDS; output transform in registers, then the direct kernel's
 //     epilogues (plain + bias + residual, or the partial-convolution one with its mask box sum, next-layer BN, update mask) on the
 //     2x2 pixels, per-channel constants from an LDS table, the residual requested before the exchange.
-// 2.25x fewer MFMAs than the direct kernel per output; the transforms are additions only.  Accuracy: per layer 2 - 4x the direct fp32
-// kernel's error against fp64 (tests/test_gpu_conv_f32.py measures both); what that does to whole frames of an ill-conditioned network
+// 2.25x fewer MFMAs than the direct kernel per output; the transforms are additions only.  Accuracy: per layer 0.8 - 3.6x a plain fp32
+// convolution's error against fp64 and, from 16 input channels on, 0.26 - 0.74x the direct fp32 kernel's (tests/test_gpu_conv_wino.py holds every
+// path of this kernel to fp64 and measures all three: profiles/conv_wino_range.txt); what its different rounding does to whole frames of an ill-conditioned network
 // is in DESIGN.md 3.4 -- the reason this is a rung of its own (convs="fp32-winograd"), not the strict fp32 rung.
 #pragma once
 #include <type_traits>

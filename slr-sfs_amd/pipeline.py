@@ -115,7 +115,7 @@ def _render(owner, clip, frames, batch, overlap, decode, policy, on_frame, one_b
     """The frame loop of both animators.  decode(gen, afl) -> the batch's outputs; store(pos, outputs) puts them at
     positions ``pos`` (indices into ``frames``).  ``policy`` (CONV_POLICIES):
       "fp32"  every convolution on this package's fp32 matrix-core kernels (v_mfma_f32_32x32x2_f32): the reference's arithmetic;
-      "fp32-winograd"  the same rung with its 3x3 layers as Winograd F(2x2, 3x3): 1.4x the clip rate of "fp32", 2 - 4x its rounding error
+      "fp32-winograd"  the same rung with its 3x3 layers as Winograd F(2x2, 3x3): 1.4x the clip rate of "fp32", per layer 1 - 4x a plain fp32 convolution's rounding error
               per layer (nets.fp32_kernels: what that means for whole frames);
       "split" split-f16 matrix-core kernels; an activation outside their exact range raises after the clip;
       "auto"  split-f16 kernels; every decoder batch leaves an asynchronous record of the device's saturation counter
