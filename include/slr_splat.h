@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 15
+#define SLR_ABI_VERSION 16
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -643,6 +643,59 @@ int slr_conv3x3_weight_grad(const float *x, const float *g, float *dw, float *db
  * NULL = 1: the plain convolution's bias gradient).  gr or db may be NULL (not both); gr needs r; ws is needed with db. */
 int slr_conv_grad_scale_bias(const float *g, const float *r, const float *um, float *gr, float *db, int N, int C, int H, int W,
                              int layout, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ trainable decoder block (ABI 16; csrc/block_grad.hip)
+ * What ResNet_Block_Pconv2 (models/layers/blocks.py:218-248) needs in training mode beyond its 3x3 convolutions: the partial batch-norm
+ * with noise-conditioned gain and bias (models/layers/normalization.py:19-52, 256-354) forward and backward, the weight gradient of the
+ * 1x1 skip convolution, and the adjoints of the two resampling stages.  b8 = 1: the [N,C,H,W] tensors are channel-blocked, [N,C/8,H,W,8]
+ * (C % 8 == 0, 16-byte aligned); masks are [N,1,H,W] (or NULL), tables [N,C] or [C] plain.  N * C <= 65535, N * C * H * W < 2^31 - 1024.  None
+ * synchronises, none uses atomics: every sum is taken in double in a fixed order, the same inputs give the same bits. */
+
+/* Workspace of slr_bn_batch_stats and slr_bn_relu_mask_backward in bytes (256-byte aligned, else SLR_E_WORKSPACE); 0 for sizes they refuse. */
+size_t slr_bn_train_ws_bytes(int N, int C, int H, int W);
+
+/* Batch statistics (normalization.py:319-335): per channel sum x and sum x^2 over ALL N H W elements, divided by
+ * count = N H W (mask NULL: manual_bn) or sum(mask) + eps (mask [N,1,H,W]: partial_manual_bn);
+ * mean[C] = sum x / count, var[C] = sum x^2 / count - mean^2, formed from the double sums and rounded once; count[1]. */
+int slr_bn_batch_stats(const float *x, const float *mask, float eps, float *mean, float *var, float *count,
+                       int N, int C, int H, int W, int b8, void *ws, size_t ws_bytes, void *stream);
+
+/* scale[n,c] = rsqrt(var[c] + eps) * gain[n,c], shift[n,c] = mean[c] * scale[n,c] - bias[n,c] (normalization.py:342-354), one fp32
+ * rounding per operation; gain / bias [N,C] or NULL (1 / 0). */
+int slr_bn_train_tables(const float *mean, const float *var, const float *gain, const float *bias, float eps,
+                        float *scale, float *shift, int N, int C, void *stream);
+
+/* a = relu(x * scale[n,c] - shift[n,c]) * mask (blocks.py:225-231 with partialconv2d.py:69), bit-equal to that fp32 expression;
+ * mask [N,1,H,W] or NULL (no mask).  slr_bn_relu_mask is the per-channel-table form of the inference path. */
+int slr_bn_relu_mask_train(const float *x, const float *scale, const float *shift, const float *mask, float *a,
+                           int N, int C, int H, int W, int b8, void *stream);
+
+/* Backward of the two calls above for the gradient ga at a.  gy = ga * mask * [x * scale - shift > 0] (the gate is recomputed from x);
+ * s0[n,c] = sum gy, s1[n,c] = sum gy * x;  dbias = s0, dgain = rs (s1 - m s0) with rs = (var + eps)^-1/2, both [N,C];
+ * dx = gy * scale + A + B (x - m) + addend, A = -rs P / count, B = -rs^3 (Q - m P) / count, P = sum_n gain s0, Q = sum_n gain s1
+ * (the gradient through mean and var = m2 - m^2 of slr_bn_batch_stats).  stored = 1: mean / var are stored statistics, A = B = 0 and
+ * `count` is not read.  addend [N,C,H,W] in x's layout or NULL; dx, dgain, dbias may each be NULL (not all); gain NULL = 1.
+ * ws is needed unless stored = 1 and dgain = dbias = NULL. */
+int slr_bn_relu_mask_backward(const float *x, const float *ga, const float *mask, const float *scale, const float *shift,
+                              const float *mean, const float *var, const float *gain, const float *count, float eps,
+                              const float *addend, float *dx, float *dgain, float *dbias, int stored,
+                              int N, int C, int H, int W, int b8, void *ws, size_t ws_bytes, void *stream);
+
+/* Weight gradient of out = conv1x1(x, w): dw[co][ci] = sum_{n,p} g[n,co,p] * x[n,ci,p], plain [Cout,Cin]; any Cin, Cout, H, W >= 1.
+ * fp32 products and sums on v_mfma_f32_32x32x2_f32 inside a slab of pixels, the S slabs added in double in slab order.  splits: 0 = the
+ * library's choice min(ceil(256 / channel tiles), chunks, 8 MiB / (4 Cout Cin)) with chunks = N * ceil(H W / 32) and channel tiles =
+ * ceil(Cin / 64) * ceil(Cout / 128) (csrc/slr_tuning.hpp), > 0 = that many (at most one per chunk, at most 65535).
+ * layout: SLR_GRAD_X_B8 | SLR_GRAD_G_B8.  ws: al256(S * Cout * Cin * 4) bytes, 256-byte aligned.  The bias gradient is
+ * slr_conv_grad_scale_bias; the gradient to x is slr_conv1x1_forward with the transposed weight (SLR_CONV_F32). */
+size_t slr_conv1x1_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int splits);
+int slr_conv1x1_weight_grad(const float *x, const float *g, float *dw, int N, int Cin, int Cout, int H, int W,
+                            int splits, int layout, void *ws, size_t ws_bytes, void *stream);
+
+/* The exact adjoints of slr_avgpool3x3s2 and slr_upsample_bilinear2x in gather form: g is the gradient at the resampled tensor
+ * ([N,C,(H-1)/2+1,(W-1)/2+1] / [N,C,2H,2W]), gin [N,C,H,W] the gradient at its input; every element of gin sums its own (at most 2 x 2 /
+ * 4 x 4) contributions in a fixed order, the border clamping of align_corners = False folded into the weights. */
+int slr_avgpool3x3s2_backward(const float *g, float *gin, int N, int C, int H, int W, int b8, void *stream);
+int slr_upsample_bilinear2x_backward(const float *g, float *gin, int N, int C, int H, int W, int b8, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ from . import softsplat, euler_integration_manipulator, synthesis, nets, pipelin
 from .training import splat_blend, TrainingSynthesis  # noqa: F401
 from .losses import SynthesisLoss, PerceptualLoss, L1LossWrapper, VGG19Features, load_vgg19_state_dict  # noqa: F401
 from .trainable import conv3x3, partial_conv3x3, TrainableConv3x3, TrainablePartialConv3x3  # noqa: F401
+from .trainable import (bn_relu_mask_train, conv1x1, avgpool_down, upsample_up, TrainableConv1x1, TrainableNoiseBN,  # noqa: F401
+                        TrainablePconvResBlock)
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401
 from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all  # noqa: F401
 from .dropin import install_into_reference  # noqa: F401

@@ -99,6 +99,21 @@ inline long long slr_wgrad_auto_splits(long long chunks, long long channel_tiles
 }
 #endif
 
+// ---- weight gradient of the 1x1 skip convolution (block_grad.hip): HBM-bound, so the slabs' partial sums count against the inputs' bytes
+#define SLR_WGRAD1_SLOTS 256    // workgroups of a launch: one per CU (a workgroup streams its slab with the next chunk's loads in flight) ...
+#define SLR_WGRAD1_WS_MB 8      // ... while the partial sums ([slab][Cout][Cin] fp32, written once and read once) stay within this: 64 -> 128 on
+                                // 2 x 256 x 256 moves 100 MB of X and G and 2 x 8 MB of partial sums.  Chosen by this arithmetic, not by a sweep; measured with
+                                // these values: 37.8 us = 2.9 TB/s, 36 % of the roofline, + 20.4 us of sum kernel over the 256 slabs
+#ifdef __cplusplus
+inline long long slr_wgrad1x1_auto_splits(long long chunks, long long channel_tiles, long long bytes_per_slab) {
+    long long s = (SLR_WGRAD1_SLOTS + channel_tiles - 1) / channel_tiles;
+    const long long cap = ((long long)SLR_WGRAD1_WS_MB << 20) / bytes_per_slab;
+    if (s > cap) s = cap;
+    if (s > chunks) s = chunks;
+    return s < 1 ? 1 : s;
+}
+#endif
+
 // ---- development aids
 
 // ---- variant builds (csrc/Makefile: TUNE="NAME=value ...")

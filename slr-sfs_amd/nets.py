@@ -750,6 +750,10 @@ def _load_bn(bn, sd, key):
     """key = '...bn' or '...pbn' of a (Partial)LinearNoiseLayer; zero noise -> gain 1, bias 0."""
     bn.stored_mean.copy_(sd[key + ".stored_mean"])
     bn.stored_var.copy_(sd[key + ".stored_var"])
+    if isinstance(getattr(bn, "gain", None), nn.Linear):          # trainable.TrainableNoiseBN: the noise layers next to the statistics
+        layer = key.rsplit(".", 1)[0]
+        bn.gain.weight.copy_(_fold_sn(sd, layer + ".gain"))
+        bn.bias.weight.copy_(_fold_sn(sd, layer + ".bias"))
 
 
 def _load_conv(conv, sd, key):

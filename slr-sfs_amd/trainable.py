@@ -1,5 +1,6 @@
-"""3x3 convolutions whose weights learn: the plain and the partial 3x3 / stride 1 / pad 1 convolution of the reference's decoder
-(models/layers/blocks.py:66-87, models/layers/partialconv2d.py:41-81) as differentiable operators in input, weight and bias.
+"""The decoder block whose weights learn.  First its 3x3 convolutions: the plain and the partial 3x3 / stride 1 / pad 1 convolution of the
+reference's decoder (models/layers/blocks.py:66-87, models/layers/partialconv2d.py:41-81) as differentiable operators in input, weight and
+bias.
 
 Forward: the package's fp32 rung (``nets.fp32_kernels(winograd=False)``: fp32 operands, products and accumulation on the matrix cores, the
 arithmetic of ``nn.Conv2d``).  Backward: the gradient to the input is the same forward kernel with flipped, transposed weights; weight and
@@ -7,8 +8,12 @@ bias gradients come from ``slr_conv3x3_weight_grad`` / ``slr_conv_grad_scale_bia
 asks for is computed.  Nothing synchronises; every result has the same bits from run to run.  There is no fallback: CPU tensors raise, a
 missing library raises.
 
-Not here (compositions on top of this primitive): batch-statistics BN, spectral normalisation, the 1x1 skip branch, the
-backward of pooling / up-sampling, and BN + ReLU fused into the backward's prologue.
+Then the rest of ResNet_Block_Pconv2 in training mode (blocks.py:173-248; csrc/block_grad.hip): the noise-conditioned
+(partial) batch-norm with batch statistics + ReLU + mask (``bn_relu_mask_train``, ``TrainableNoiseBN``), the 1x1 skip convolution
+(``conv1x1``), differentiable ``avgpool_down`` / ``upsample_up``, and the block itself (``TrainablePconvResBlock``).
+
+Not here: the per-element mask (x != 0) of the decoder's first block, spectral normalisation, the decoders and encoders
+as trainable wholes, and BN + ReLU fused into the backward convolution's prologue.
 """
 import torch
 import torch.nn.functional as F
@@ -20,9 +25,9 @@ from ._lib import call, lib, require_device
 GRAD_X_B8, GRAD_G_B8 = 1, 2              # include/slr_splat.h: SLR_GRAD_X_B8 / SLR_GRAD_G_B8
 
 
-def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False):
+def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False, k=3, residual=None):
     """Types, device, dtype, shapes and layouts -- before anything touches the device."""
-    tensors = (x, weight, bias, mask)
+    tensors = (x, weight, bias, mask, residual)
     for t in tensors:
         if t is not None and not torch.is_tensor(t):
             raise TypeError(f"slr_sfs_amd.{name}: tensors required, got {type(t).__name__}")
@@ -35,8 +40,8 @@ def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False):
     if x.dim() != 4 or min(x.shape) < 1:
         raise ValueError(f"{name}: input [N,Cin,H,W] with N, Cin, H, W >= 1 required, got {tuple(x.shape)}")
     N, cin, H, W = x.shape
-    if weight.dim() != 4 or tuple(weight.shape[1:]) != (cin, 3, 3) or weight.shape[0] < 1:
-        raise ValueError(f"{name}: weight {tuple(weight.shape)}, expected [Cout,{cin},3,3]")
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (cin, k, k) or weight.shape[0] < 1:
+        raise ValueError(f"{name}: weight {tuple(weight.shape)}, expected [Cout,{cin},{k},{k}]")
     cout = weight.shape[0]
     if bias is not None and tuple(bias.shape) != (cout,):
         raise ValueError(f"{name}: bias {tuple(bias.shape)}, expected ({cout},)")
@@ -46,7 +51,9 @@ def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False):
         raise ValueError(f"{name}: a channel-blocked input needs Cin % 8 == 0, got {cin}")
     if out_b8 and cout % 8:
         raise ValueError(f"{name}: a channel-blocked output needs Cout % 8 == 0, got {cout}")
-    for label, t in (("input", x), ("weight", weight), ("bias", bias), ("mask", mask)):
+    if residual is not None and tuple(residual.shape) != (N, cout, H, W):
+        raise ValueError(f"{name}: residual {tuple(residual.shape)}, expected {(N, cout, H, W)}")
+    for label, t in (("input", x), ("weight", weight), ("bias", bias), ("mask", mask), ("residual", residual)):
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{name}: {label} is not contiguous")
     require_device(*tensors)
@@ -60,7 +67,7 @@ class _Prepared(nets.Conv):
         nn.Module.__init__(self)
         object.__setattr__(self, "weight", weight)      # (not registered: the tensor stays its owner's)
         object.__setattr__(self, "bias", None)
-        self.cin, self.k, self.pad = weight.shape[1], 3, 1
+        self.cin, self.k, self.pad = weight.shape[1], weight.shape[2], weight.shape[2] // 2
 
 
 def _owner_of(weight, owner):
@@ -173,46 +180,49 @@ def partial_conv_factors(mask, cin):
 
 class _PartialConv3x3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xm, mask, weight, bias, owner):
+    def forward(ctx, xm, mask, weight, bias, owner, residual=None, in_b8=False, out_b8=False):
         N, cin, H, W = xm.shape
         cout = weight.shape[0]
         buf, arith = _forward_weights(weight, owner)
         out, um = xm.new_empty(N, cout, H, W), xm.new_empty(N, 1, H, W)
-        call("slr_pconv3x3_forward", xm.device, xm, None, None, mask, buf, 1.0, 1.0, bias, None, None, None, out, um,
-             N, cin, cout, H, W, arith)
+        layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0) | (nets.RES_B8 if out_b8 and residual is not None else 0)
+        call("slr_pconv3x3_forward", xm.device, xm, None, None, mask, buf, 1.0, 1.0, bias, residual, None, None, out, um,
+             N, cin, cout, H, W, layout | arith)
         ctx.save_for_backward(xm, mask, weight)
-        ctx.owner = owner
+        ctx.owner, ctx.layouts = owner, (in_b8, out_b8)
         ctx.mark_non_differentiable(um)
         return out, um
 
     @staticmethod
     def backward(ctx, g, _g_um):
         xm, mask, weight = ctx.saved_tensors
-        owner = ctx.owner
+        owner, (in_b8, out_b8) = ctx.owner, ctx.layouts
         g = g.contiguous()
         require_device(g)
         cout, cin = weight.shape[:2]
         need_x, _, need_w, need_b = ctx.needs_input_grad[:4]
         gx = gw = gb = None
+        glayout = GRAD_G_B8 if out_b8 else 0
         if need_x or need_w or need_b:
             r, um = partial_conv_factors(mask, cin)
-            gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b)
+            gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
             if need_x:
                 buf, arith = _backward_weights(weight, owner)
-                gx = _conv(gr, buf, arith, None, cin, 0)
+                gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
             if need_w:
-                gw, _ = _weight_grad(xm, gr, cout, False, 0)
-        return gx, None, gw, gb, None
+                gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
+        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None    # (out = ... + residual)
 
 
-def partial_conv3x3(xm, mask, weight, bias, *, _owner=None):
+def partial_conv3x3(xm, mask, weight, bias, *, residual=None, in_b8=False, out_b8=False, _owner=None):
     """``nets.PartialConv.forward(xm, mask, pre_bn=None)``: PartialConv2d(multi_channel=True, return_mask=True) (partialconv2d.py:41-81)
     of the already activated and masked ``xm`` [N,Cin,H,W] with the channel-uniform ``mask`` [N,1,H,W]; returns (out, update_mask).
-    Differentiable in xm, weight and bias; mask and update_mask carry no gradient.  NCHW tensors."""
+    Differentiable in xm, weight and bias; mask and update_mask carry no gradient.  ``residual`` [N,Cout,H,W] (in the result's layout) is
+    added in the kernel's epilogue (blocks.py:248) and receives the result's gradient.  in_b8 / out_b8 as ``conv3x3``."""
     if bias is None:
         raise ValueError("partial_conv3x3: a bias is required (PartialConv2d adds it inside the mask ratio)")
-    _check("partial_conv3x3", xm, weight, bias, mask=mask)
-    return _PartialConv3x3.apply(xm, mask.detach(), weight, bias, _owner)
+    _check("partial_conv3x3", xm, weight, bias, mask=mask, in_b8=in_b8, out_b8=out_b8, residual=residual)
+    return _PartialConv3x3.apply(xm, mask.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8))
 
 
 class TrainableConv3x3(nets.Conv):
@@ -237,5 +247,269 @@ class TrainablePartialConv3x3(nets.PartialConv):
         self.weight.requires_grad_(True)
         self.bias.requires_grad_(True)
 
-    def forward(self, xm, mask):
-        return partial_conv3x3(xm, mask, self.weight, self.bias, _owner=self)
+    def forward(self, xm, mask, residual=None, in_b8=False, out_b8=False):
+        return partial_conv3x3(xm, mask, self.weight, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self)
+
+
+# --------------------------------------------------------------------------- the rest of the block (csrc/block_grad.hip)
+
+def _check_planes(name, x, b8, mask=None, tables=(), like=()):
+    """The same checks for the operators on [N,C,H,W] planes: ``tables`` are [N,C], ``like`` tensors of x's shape."""
+    tensors = (x, mask, *tables, *like)
+    for t in tensors:
+        if t is not None and not torch.is_tensor(t):
+            raise TypeError(f"slr_sfs_amd.{name}: tensors required, got {type(t).__name__}")
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError("slr_sfs_amd operators run on ROCm device tensors only (no CPU path)")
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"slr_sfs_amd: float32 tensors required, got {t.dtype}")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{name}: input [N,C,H,W] with N, C, H, W >= 1 required, got {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    if mask is not None and tuple(mask.shape) != (N, 1, H, W):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)}, expected {(N, 1, H, W)}")
+    for t in tables:
+        if t is not None and tuple(t.shape) != (N, C):
+            raise ValueError(f"{name}: gain / bias {tuple(t.shape)}, expected {(N, C)}")
+    for t in like:
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"{name}: {tuple(t.shape)}, expected {tuple(x.shape)}")
+    if b8 and C % 8:
+        raise ValueError(f"{name}: a channel-blocked tensor needs C % 8 == 0, got {C}")
+    if N * C > 65535:
+        raise ValueError(f"{name}: N * C <= 65535 required, got {N * C}")
+    for t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: a tensor is not contiguous")
+    require_device(*tensors)
+
+
+def _bn_ws(x):
+    return torch.empty(int(lib().slr_bn_train_ws_bytes(*x.shape)), dtype=torch.uint8, device=x.device)
+
+
+class _BnReluMaskTrain(torch.autograd.Function):
+    """(a, mean, var[, x]) -- with ``fork`` the input comes back as a second output whose gradient the backward adds to dx in its
+    elementwise pass (the block input feeds bn1 and the skip branch)."""
+
+    @staticmethod
+    def forward(ctx, x, mask, gain, bias, mean, var, eps, b8, fork):
+        N, C, H, W = x.shape
+        stored = mean is not None
+        count = None
+        if not stored:
+            mean, var, count = x.new_empty(C), x.new_empty(C), x.new_empty(1)
+            ws = _bn_ws(x)
+            call("slr_bn_batch_stats", x.device, x, mask, eps, mean, var, count, N, C, H, W, int(b8), ws, ws.numel())
+        scale, shift = x.new_empty(N, C), x.new_empty(N, C)
+        call("slr_bn_train_tables", x.device, mean, var, gain, bias, eps, scale, shift, N, C)
+        a = torch.empty_like(x)
+        call("slr_bn_relu_mask_train", x.device, x, scale, shift, mask, a, N, C, H, W, int(b8))
+        ctx.save_for_backward(x, mask, gain, scale, shift, mean, var, count)
+        ctx.cfg = (eps, b8, stored, bias is not None)
+        ctx.set_materialize_grads(False)
+        if stored:
+            return (a, None, None, x) if fork else (a, None, None)
+        ctx.mark_non_differentiable(mean, var)
+        return (a, mean, var, x) if fork else (a, mean, var)
+
+    @staticmethod
+    def backward(ctx, ga, _gm=None, _gv=None, gskip=None):
+        x, mask, gain, scale, shift, mean, var, count = ctx.saved_tensors
+        eps, b8, stored, has_bias = ctx.cfg
+        N, C, H, W = x.shape
+        need_x, need_g, need_b = ctx.needs_input_grad[0], gain is not None and ctx.needs_input_grad[2], has_bias and ctx.needs_input_grad[3]
+        if ga is None:                                   # only the skip branch was used
+            return (gskip if need_x else None), None, None, None, None, None, None, None, None
+        ga = ga.contiguous()
+        require_device(ga)
+        addend = None
+        if need_x and gskip is not None:
+            addend = gskip.contiguous()
+            require_device(addend)
+        dx = torch.empty_like(x) if need_x else None
+        dgain = x.new_empty(N, C) if need_g else None
+        dbias = x.new_empty(N, C) if need_b else None
+        if dx is None and dgain is None and dbias is None:
+            return (None,) * 9
+        ws = _bn_ws(x) if (not stored or need_g or need_b) else None
+        call("slr_bn_relu_mask_backward", x.device, x, ga, mask, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias,
+             int(stored), N, C, H, W, int(b8), ws, 0 if ws is None else ws.numel())
+        return dx, None, dgain, dbias, None, None, None, None, None
+
+
+def bn_relu_mask_train(x, mask, gain, bias, *, mean=None, var=None, eps=1e-5, b8=False, fork=False):
+    """relu(bn(x)) * mask of the block in training mode (blocks.py:225-231 with normalization.py:276-354 and partialconv2d.py:69):
+    scale = rsqrt(var + eps) * gain, shift = mean * scale - bias, a = relu(x * scale - shift) * mask, with the batch statistics
+    mean = sum x / cnt, var = sum x^2 / cnt - mean^2 over ALL elements of a channel and cnt = N H W (``mask`` None: manual_bn) or
+    sum(mask) + eps (``mask`` [N,1,H,W]: partial_manual_bn).  ``gain`` / ``bias``: [N,C] per-sample tables, or None = 1 / 0.  Passing
+    ``mean`` and ``var`` [C] selects stored statistics (eval mode).  Returns (a, mean, var); differentiable in x, gain and bias -- the
+    gradient to x includes the one through the batch statistics.  b8: x and a are channel-blocked.
+    fork=True returns (a, mean, var, x): x again as an output of the same node, for a second consumer of x (the block's skip branch).  The
+    gradient arriving at that output is added to dx inside the backward's elementwise pass (the entry point's ``addend``) instead of
+    in a pass of its own by autograd."""
+    _check_planes("bn_relu_mask_train", x, b8, mask, (gain, bias))
+    if (mean is None) != (var is None):
+        raise ValueError("bn_relu_mask_train: mean and var go together")
+    if mean is not None:
+        for t in (mean, var):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
+                raise ValueError(f"bn_relu_mask_train: mean / var: contiguous float32 device tensors ({x.shape[1]},) required")
+        mean, var = mean.detach(), var.detach()
+    out = _BnReluMaskTrain.apply(x, None if mask is None else mask.detach(), gain, bias, mean, var, float(eps), bool(b8), bool(fork))
+    if mean is not None:
+        out = (out[0], mean, var) + tuple(out[3:])
+    return out
+
+
+class _Conv1x1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, in_b8, out_b8, owner):
+        buf, arith = _forward_weights(weight, owner)
+        out = _conv1(x, buf, arith, bias, weight.shape[0], (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0))
+        ctx.save_for_backward(x, weight)
+        ctx.cfg = (in_b8, out_b8, owner, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        in_b8, out_b8, owner, has_bias = ctx.cfg
+        g = g.contiguous()
+        require_device(g)
+        N, cin, H, W = x.shape
+        cout = weight.shape[0]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        gx = gw = gb = None
+        if need_x:                                       # the forward kernel with the transposed weight
+            buf, arith = _backward_weights(weight, owner)
+            gx = _conv1(g, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
+        glayout = GRAD_G_B8 if out_b8 else 0
+        if need_w:
+            gw = x.new_empty(cout, cin, 1, 1)
+            ws = torch.empty(int(lib().slr_conv1x1_grad_ws_bytes(N, cin, cout, H, W, 0)), dtype=torch.uint8, device=x.device)
+            call("slr_conv1x1_weight_grad", x.device, x, g, gw, N, cin, cout, H, W, 0, (GRAD_X_B8 if in_b8 else 0) | glayout, ws, ws.numel())
+        if need_b:
+            _, gb = _scale_bias(g, None, None, False, True, glayout)
+        return gx, gw, gb, None, None, None
+
+
+def _conv1(x, buf, arith, bias, cout, layout):
+    N, cin, H, W = x.shape
+    out = x.new_empty(N, cout, H, W)
+    call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, 1.0, 1.0, layout | arith)
+    return out
+
+
+def conv1x1(x, weight, bias=None, *, in_b8=False, out_b8=False, _owner=None):
+    """conv2d(x, weight, bias) for a 1x1 ``weight`` [Cout,Cin,1,1] (the block's skip branch, blocks.py:192-193, 243-247) on the fp32 rung,
+    differentiable in x, weight and bias; in_b8 / out_b8 as ``conv3x3``."""
+    _check("conv1x1", x, weight, bias, in_b8=in_b8, out_b8=out_b8, k=1)
+    return _Conv1x1.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner)
+
+
+class _Resample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, up, b8):
+        N, C, H, W = x.shape
+        out = x.new_empty(N, C, 2 * H, 2 * W) if up else x.new_empty(N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+        call("slr_upsample_bilinear2x" if up else "slr_avgpool3x3s2", x.device, x, out, N, C, H, W, int(b8))
+        ctx.cfg = (tuple(x.shape), up, b8)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (N, C, H, W), up, b8 = ctx.cfg
+        g = g.contiguous()
+        require_device(g)
+        gin = g.new_empty(N, C, H, W)
+        call("slr_upsample_bilinear2x_backward" if up else "slr_avgpool3x3s2_backward", g.device, g, gin, N, C, H, W, int(b8))
+        return gin, None, None
+
+
+def avgpool_down(x, b8=False):
+    """nn.AvgPool2d(3, stride=2, padding=1) (blocks.py:196-199), differentiable; b8: x and the result are channel-blocked."""
+    _check_planes("avgpool_down", x, b8)
+    return _Resample.apply(x, False, bool(b8))
+
+
+def upsample_up(x, b8=False):
+    """nn.Upsample(scale_factor=2, mode='bilinear') (blocks.py:200-203), differentiable; b8: x and the result are channel-blocked."""
+    _check_planes("upsample_up", x, b8)
+    return _Resample.apply(x, True, bool(b8))
+
+
+class TrainableConv1x1(nets.Conv):
+    """``nets.Conv(cin, cout, 1)`` whose parameters learn (the block's ``conv_b``)."""
+
+    def __init__(self, cin, cout, bias=False):
+        super().__init__(cin, cout, 1, bias)
+        self.weight.requires_grad_(True)
+        if self.bias is not None:
+            self.bias.requires_grad_(True)
+
+    def forward(self, x, in_b8=False, out_b8=False):
+        return conv1x1(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self)
+
+
+class TrainableNoiseBN(nn.Module):
+    """(Partial)LinearNoiseLayer + ReLU + mask (normalization.py:19-90, 157-354): ``nets.AffineBN``'s buffers ``stored_mean`` /
+    ``stored_var`` plus the two bias-free linear maps ``gain`` and ``bias`` from the noise [N,noise_sz] (torch ops: [N,20] x [20,C] is
+    not tensor-sized).  Training: batch statistics, the stored ones updated with momentum 0.1; eval: stored statistics, zero noise."""
+
+    def __init__(self, ch, noise_sz=20, eps=1e-5, momentum=0.1):
+        super().__init__()
+        self.eps, self.momentum, self.noise_sz = eps, momentum, noise_sz
+        self.register_buffer("stored_mean", torch.zeros(ch))
+        self.register_buffer("stored_var", torch.ones(ch))
+        self.gain, self.bias = nn.Linear(noise_sz, ch, bias=False), nn.Linear(noise_sz, ch, bias=False)
+
+    def forward(self, x, mask, noise=None, b8=False, fork=False):
+        """relu(bn(x)) * mask (``mask`` None: no mask, the plain BN of the encoder blocks).  ``noise`` [N,noise_sz]; None draws
+        torch.randn in training mode and means zeros in eval mode.  Returns ``bn_relu_mask_train``'s tuple; b8 and fork as there."""
+        if noise is None:
+            noise = (torch.randn if self.training else torch.zeros)(x.shape[0], self.noise_sz, device=x.device, dtype=x.dtype)
+        gain, bias = (1.0 + self.gain(noise)).contiguous(), self.bias(noise).contiguous()
+        if not self.training:
+            return bn_relu_mask_train(x, mask, gain, bias, mean=self.stored_mean, var=self.stored_var, eps=self.eps, b8=b8, fork=fork)
+        out = bn_relu_mask_train(x, mask, gain, bias, eps=self.eps, b8=b8, fork=fork)
+        with torch.no_grad():                            # normalization.py:287-300
+            self.stored_mean.mul_(1.0 - self.momentum).add_(out[1], alpha=self.momentum)
+            self.stored_var.mul_(1.0 - self.momentum).add_(out[2], alpha=self.momentum)
+        return out
+
+
+class TrainablePconvResBlock(nets.PconvResBlock):
+    """``nets.PconvResBlock`` (ResNet_Block_Pconv2 with pconv_pbn_woresbias, blocks.py:173-248) as one differentiable unit in training or
+    eval mode: same sub-module names and state-dict keys (``nets.load_reference_state_dict`` fills it), the BNs with their noise weights
+    ``bn1.gain.weight`` ... as extra keys."""
+
+    def __init__(self, cin, cout, resample=None):
+        super().__init__(cin, cout, resample)
+        self.bn1, self.bn2 = TrainableNoiseBN(cin), TrainableNoiseBN(cout)
+        self.conv_aa, self.conv_ab = TrainablePartialConv3x3(cin, cout), TrainablePartialConv3x3(cout, cout)
+        self.conv_b = TrainableConv1x1(cin, cout) if self.conv_b is not None else None
+        self.kind = resample
+
+    def forward(self, x, mask, b8_in=False, noise=None):
+        """-> (y, update_mask, b8_out).  ``mask`` [N,1,H,W] channel-uniform; ``b8_in`` / ``b8_out``: x / y are channel-blocked;
+        ``noise`` None or the pair (noise1, noise2) of the two BNs.  bn1 -> conv_aa -> bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue ->
+        one resampling of the sum (both resamplers are linear, as in ``nets.PconvResBlock``) -> the mask resampled."""
+        if mask is None:
+            raise ValueError("TrainablePconvResBlock: an explicit mask [N,1,H,W] is required (the per-element mask x != 0 is not trainable yet)")
+        _check_planes("TrainablePconvResBlock", x, b8_in, mask)
+        cout = self.conv_aa.weight.shape[0]
+        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
+        n1, n2 = noise if noise is not None else (None, None)
+        a, _, _, xs = self.bn1(x, mask, n1, b8=b8_in, fork=True)                    # blocks.py:225-231
+        a, m = self.conv_aa(a, mask, in_b8=b8_in, out_b8=b8)
+        a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238
+        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs        # :243-247
+        a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)                # :239, 248
+        if self.kind == "Up":
+            a = upsample_up(a, b8)
+        elif self.kind:
+            a = avgpool_down(a, b8)
+        return a, self.resample_mask(m), b8
