@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 16
+#define SLR_ABI_VERSION 17
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -696,6 +696,47 @@ int slr_conv1x1_weight_grad(const float *x, const float *g, float *dw, int N, in
  * 4 x 4) contributions in a fixed order, the border clamping of align_corners = False folded into the weights. */
 int slr_avgpool3x3s2_backward(const float *g, float *gin, int N, int C, int H, int W, int b8, void *stream);
 int slr_upsample_bilinear2x_backward(const float *g, float *gin, int N, int C, int H, int W, int b8, void *stream);
+
+/* ------------------------------------------------------------------ the decoder's first block, trainable (ABI 17; csrc/decoder_grad.hip)
+ * ResNetDecoderPconv2 calls its first ResNet_Block_Pconv2 with the per-element mask (x != 0).float() [N,C,H,W]
+ * (models/networks/architectures.py:369).  The entry points below are that block's batch-norm and the epilogue of its first partial
+ * convolution with k = [x != 0] recomputed from x wherever it is needed: the mask is never a tensor.  From the update mask of that
+ * convolution on, the mask is channel-uniform and the ABI 16 entry points apply.  Layouts, size limits (N * C <= 65535,
+ * N * C * H * W < 2^31 - 1024) and rules as there: no atomics, every sum in double in a fixed order, nothing synchronises.  The two
+ * reduction passes take 8 items per thread before their one workgroup sum. */
+
+/* Workspace of the statistics and the backward below in bytes (256-byte aligned, else SLR_E_WORKSPACE); 0 for sizes they refuse. */
+size_t slr_bn_nonzero_ws_bytes(int N, int C, int H, int W);
+
+/* Batch statistics of partial_manual_bn with a [N,C,H,W] mask (models/layers/normalization.py:319-335): per channel
+ * count[c] = #{x != 0} + eps (the number is an integer sum, eps is added in double), mean[c] = sum x / count[c],
+ * var[c] = sum x^2 / count[c] - mean^2; the sums over ALL elements equal those over the kept ones.  mean, var, count: [C]. */
+int slr_bn_nonzero_stats(const float *x, float eps, float *mean, float *var, float *count,
+                         int N, int C, int H, int W, int b8, void *ws, size_t ws_bytes, void *stream);
+
+/* msum [N,1,H,W] = sum_c [x != 0]: all a partial convolution needs of the per-element mask (models/layers/partialconv2d.py:61-67,
+ * conv2d(mask, ones) = box3x3(msum)).  Exact integers in fp32; msum is plain in either layout of x. */
+int slr_nonzero_count_plane(const float *x, float *msum, int N, int C, int H, int W, int b8, void *stream);
+
+/* a = relu(x * scale[n,c] - shift[n,c]) * [x != 0] (models/layers/blocks.py:225-231 with partialconv2d.py:69), bit-equal to that fp32
+ * expression; scale, shift [N,C] from slr_bn_train_tables. */
+int slr_bn_relu_nonzero_train(const float *x, const float *scale, const float *shift, float *a,
+                              int N, int C, int H, int W, int b8, void *stream);
+
+/* Backward of the calls above: slr_bn_relu_mask_backward with gy = ga * [x != 0] * [x * scale - shift > 0] and the per-channel
+ * count [C] of slr_bn_nonzero_stats.  The term A + B (x - m) of dx reaches the zero elements too, as the reference's autograd gives it.
+ * NULL outputs, `stored`, addend, gain and ws as there (ws: slr_bn_nonzero_ws_bytes). */
+int slr_bn_relu_nonzero_backward(const float *x, const float *ga, const float *scale, const float *shift,
+                                 const float *mean, const float *var, const float *gain, const float *count, float eps,
+                                 const float *addend, float *dx, float *dgain, float *dbias, int stored,
+                                 int N, int C, int H, int W, int b8, void *ws, size_t ws_bytes, void *stream);
+
+/* The epilogue of a partial convolution whose factors are given as planes (partialconv2d.py:72-74, blocks.py:248):
+ * out = (raw0 * ratio + bias[c]) * um (+ residual), fp32 in that order; ratio, um [N,1,H,W] plain, bias [C], raw0 / residual / out
+ * [N,C,H,W] in one layout (b8); residual may be NULL, out may be raw0.  For the first block ratio = 9 Cin / (box3x3(msum) + 1e-8) * um,
+ * um = clamp(box3x3(msum), 0, 1) around a bias-free slr_conv3x3_forward. */
+int slr_pconv_train_epilogue(const float *raw0, const float *ratio, const float *um, const float *bias, const float *residual,
+                             float *out, int N, int C, int H, int W, int b8, void *stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,8 @@ from .losses import SynthesisLoss, PerceptualLoss, L1LossWrapper, VGG19Features,
 from .trainable import conv3x3, partial_conv3x3, TrainableConv3x3, TrainablePartialConv3x3  # noqa: F401
 from .trainable import (bn_relu_mask_train, conv1x1, avgpool_down, upsample_up, TrainableConv1x1, TrainableNoiseBN,  # noqa: F401
                         TrainablePconvResBlock)
+from .trainable import (bn_relu_nonzero_train, partial_conv_factors_counts, partial_conv3x3_counts, TrainablePconvInputBlock,  # noqa: F401
+                        TrainableResBlock, TrainableDecoderPconv2, TrainableEncoderWithZ, TrainableEncoder, TrainableBGDecoder)
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401
 from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all  # noqa: F401
 from .dropin import install_into_reference  # noqa: F401

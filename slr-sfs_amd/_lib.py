@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 16
+ABI_VERSION = 17
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -100,6 +100,12 @@ SIGNATURES = {
     "slr_conv1x1_weight_grad": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_avgpool3x3s2_backward": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _vp]),
     "slr_upsample_bilinear2x_backward": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_bn_nonzero_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "slr_bn_nonzero_stats": (_i, [_fp, _f, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_nonzero_count_plane": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_bn_relu_nonzero_train": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_bn_relu_nonzero_backward": (_i, [_fp] * 8 + [_f] + [_fp] * 4 + [_i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_pconv_train_epilogue": (_i, [_fp] * 6 + [_i, _i, _i, _i, _i, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

@@ -12,8 +12,12 @@ Then the rest of ResNet_Block_Pconv2 in training mode (blocks.py:173-248, DESIGN
 (partial) batch-norm with batch statistics + ReLU + mask (``bn_relu_mask_train``, ``TrainableNoiseBN``), the 1x1 skip convolution
 (``conv1x1``), differentiable ``avgpool_down`` / ``upsample_up``, and the block itself (``TrainablePconvResBlock``).
 
-Not here: the per-element mask (x != 0) of the decoder's first block, spectral normalisation, the decoders and encoders
-as trainable wholes, and BN + ReLU fused into the backward convolution's prologue.
+Then the generator's networks (csrc/decoder_grad.hip): the decoder's first block, whose mask is (x != 0) per element
+(architectures.py:369) -- ``bn_relu_nonzero_train``, ``partial_conv_factors_counts``, ``partial_conv3x3_counts``,
+``TrainablePconvInputBlock`` -- the plain ``TrainableResBlock`` (ResNet_Block, blocks.py:47-87) and the nets made of the two:
+``TrainableDecoderPconv2``, ``TrainableEncoderWithZ``, ``TrainableEncoder``, ``TrainableBGDecoder``.
+
+Not here: spectral normalisation (the reference trains with --norm_G batch), and BN + ReLU fused into the backward convolution's prologue.
 """
 import torch
 import torch.nn.functional as F
@@ -96,10 +100,10 @@ def _backward_weights(weight, owner):
     return _forward_weights(bconv.weight, bconv)
 
 
-def _conv(x, buf, arith, bias, cout, layout):
+def _conv(x, buf, arith, bias, cout, layout, residual=None):
     N, cin, H, W = x.shape
     out = x.new_empty(N, cout, H, W)
-    call("slr_conv3x3_forward", x.device, x, buf, bias, None, out, N, cin, cout, H, W, 1.0, 1.0, None, None, layout | arith)
+    call("slr_conv3x3_forward", x.device, x, buf, bias, residual, out, N, cin, cout, H, W, 1.0, 1.0, None, None, layout | arith)
     return out
 
 
@@ -131,10 +135,10 @@ def _scale_bias(g, r, um, want_gr, want_bias, layout=0):
 
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, in_b8, out_b8, owner):
+    def forward(ctx, x, weight, bias, in_b8, out_b8, owner, residual=None):
         buf, arith = _forward_weights(weight, owner)
-        layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0)
-        out = _conv(x, buf, arith, bias, weight.shape[0], layout)
+        layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0) | (nets.RES_B8 if out_b8 and residual is not None else 0)
+        out = _conv(x, buf, arith, bias, weight.shape[0], layout, residual)
         ctx.save_for_backward(x, weight)
         ctx.cfg = (in_b8, out_b8, owner, bias is not None)
         return out
@@ -156,16 +160,17 @@ class _Conv3x3(torch.autograd.Function):
             gw, gb = _weight_grad(x, g, cout, need_b, (GRAD_X_B8 if in_b8 else 0) | glayout)
         elif need_b:
             _, gb = _scale_bias(g, None, None, False, True, glayout)
-        return gx, gw, gb, None, None, None
+        return gx, gw, gb, None, None, None, (g if ctx.needs_input_grad[6] else None)    # (out = ... + residual)
 
 
-def conv3x3(x, weight, bias=None, *, in_b8=False, out_b8=False, _owner=None):
+def conv3x3(x, weight, bias=None, *, in_b8=False, out_b8=False, residual=None, _owner=None):
     """conv2d(x, weight, bias, stride 1, padding 1) for a 3x3 ``weight`` [Cout,Cin,3,3], differentiable in x, weight and bias.
 
     in_b8 / out_b8: x / the result (and with them their gradients) are channel-blocked, [N,C/8,H,W,8] in memory under the logical shape
-    [N,C,H,W] -- the package's activation layout (nets._b8); C % 8 == 0 then."""
-    _check("conv3x3", x, weight, bias, in_b8=in_b8, out_b8=out_b8)
-    return _Conv3x3.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner)
+    [N,C,H,W] -- the package's activation layout (nets._b8); C % 8 == 0 then.  ``residual`` [N,Cout,H,W] (in the result's layout) is
+    added in the kernel's epilogue (the x_a + x_b of ResNet_Block, blocks.py:87) and receives the result's gradient."""
+    _check("conv3x3", x, weight, bias, in_b8=in_b8, out_b8=out_b8, residual=residual)
+    return _Conv3x3.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, residual)
 
 
 def partial_conv_factors(mask, cin):
@@ -235,8 +240,8 @@ class TrainableConv3x3(nets.Conv):
         if self.bias is not None:
             self.bias.requires_grad_(True)
 
-    def forward(self, x, in_b8=False, out_b8=False):
-        return conv3x3(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self)
+    def forward(self, x, in_b8=False, out_b8=False, residual=None):
+        return conv3x3(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self)
 
 
 class TrainablePartialConv3x3(nets.PartialConv):
@@ -466,15 +471,19 @@ class TrainableNoiseBN(nn.Module):
         self.register_buffer("stored_var", torch.ones(ch))
         self.gain, self.bias = nn.Linear(noise_sz, ch, bias=False), nn.Linear(noise_sz, ch, bias=False)
 
-    def forward(self, x, mask, noise=None, b8=False, fork=False):
+    def forward(self, x, mask, noise=None, b8=False, fork=False, nonzero=False):
         """relu(bn(x)) * mask (``mask`` None: no mask, the plain BN of the encoder blocks).  ``noise`` [N,noise_sz]; None draws
-        torch.randn in training mode and means zeros in eval mode.  Returns ``bn_relu_mask_train``'s tuple; b8 and fork as there."""
+        torch.randn in training mode and means zeros in eval mode.  Returns ``bn_relu_mask_train``'s tuple; b8 and fork as there.
+        nonzero=True (``mask`` None): the per-element mask x != 0 of the decoder's first block, ``bn_relu_nonzero_train``'s tuple."""
+        if nonzero and mask is not None:
+            raise ValueError("TrainableNoiseBN: nonzero=True derives the mask from x; pass mask=None")
         if noise is None:
             noise = (torch.randn if self.training else torch.zeros)(x.shape[0], self.noise_sz, device=x.device, dtype=x.dtype)
         gain, bias = (1.0 + self.gain(noise)).contiguous(), self.bias(noise).contiguous()
+        bn = (lambda **kw: bn_relu_nonzero_train(x, gain, bias, **kw)) if nonzero else (lambda **kw: bn_relu_mask_train(x, mask, gain, bias, **kw))
         if not self.training:
-            return bn_relu_mask_train(x, mask, gain, bias, mean=self.stored_mean, var=self.stored_var, eps=self.eps, b8=b8, fork=fork)
-        out = bn_relu_mask_train(x, mask, gain, bias, eps=self.eps, b8=b8, fork=fork)
+            return bn(mean=self.stored_mean, var=self.stored_var, eps=self.eps, b8=b8, fork=fork)
+        out = bn(eps=self.eps, b8=b8, fork=fork)
         with torch.no_grad():                            # normalization.py:287-300
             self.stored_mean.mul_(1.0 - self.momentum).add_(out[1], alpha=self.momentum)
             self.stored_var.mul_(1.0 - self.momentum).add_(out[2], alpha=self.momentum)
@@ -498,7 +507,7 @@ class TrainablePconvResBlock(nets.PconvResBlock):
         ``noise`` None or the pair (noise1, noise2) of the two BNs.  bn1 -> conv_aa -> bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue ->
         one resampling of the sum (both resamplers are linear, as in ``nets.PconvResBlock``) -> the mask resampled."""
         if mask is None:
-            raise ValueError("TrainablePconvResBlock: an explicit mask [N,1,H,W] is required (the per-element mask x != 0 is not trainable yet)")
+            raise ValueError("TrainablePconvResBlock: an explicit mask [N,1,H,W] is required (the per-element mask x != 0 is TrainablePconvInputBlock's)")
         _check_planes("TrainablePconvResBlock", x, b8_in, mask)
         cout = self.conv_aa.weight.shape[0]
         b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
@@ -513,3 +522,288 @@ class TrainablePconvResBlock(nets.PconvResBlock):
         elif self.kind:
             a = avgpool_down(a, b8)
         return a, self.resample_mask(m), b8
+
+
+# --------------------------------------------------------------------------- the decoder's first block (csrc/decoder_grad.hip)
+
+def _nz_ws(x):
+    return torch.empty(int(lib().slr_bn_nonzero_ws_bytes(*x.shape)), dtype=torch.uint8, device=x.device)
+
+
+class _BnReluNonzeroTrain(torch.autograd.Function):
+    """(a, mean, var, msum[, x]): ``_BnReluMaskTrain`` with the mask k = [x != 0] recomputed from x by every kernel."""
+
+    @staticmethod
+    def forward(ctx, x, gain, bias, mean, var, eps, b8, fork):
+        N, C, H, W = x.shape
+        stored = mean is not None
+        count = None
+        if not stored:
+            mean, var, count = x.new_empty(C), x.new_empty(C), x.new_empty(C)
+            ws = _nz_ws(x)
+            call("slr_bn_nonzero_stats", x.device, x, eps, mean, var, count, N, C, H, W, int(b8), ws, ws.numel())
+        scale, shift = x.new_empty(N, C), x.new_empty(N, C)
+        call("slr_bn_train_tables", x.device, mean, var, gain, bias, eps, scale, shift, N, C)
+        a, msum = torch.empty_like(x), x.new_empty(N, 1, H, W)
+        call("slr_bn_relu_nonzero_train", x.device, x, scale, shift, a, N, C, H, W, int(b8))
+        call("slr_nonzero_count_plane", x.device, x, msum, N, C, H, W, int(b8))
+        ctx.save_for_backward(x, gain, scale, shift, mean, var, count)
+        ctx.cfg = (eps, b8, stored, bias is not None)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(msum)
+        if stored:
+            return (a, None, None, msum, x) if fork else (a, None, None, msum)
+        ctx.mark_non_differentiable(mean, var)
+        return (a, mean, var, msum, x) if fork else (a, mean, var, msum)
+
+    @staticmethod
+    def backward(ctx, ga, _gm=None, _gv=None, _gs=None, gskip=None):
+        x, gain, scale, shift, mean, var, count = ctx.saved_tensors
+        eps, b8, stored, has_bias = ctx.cfg
+        N, C, H, W = x.shape
+        need_x, need_g, need_b = ctx.needs_input_grad[0], gain is not None and ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        if ga is None:                                   # only the skip branch was used
+            return (gskip if need_x else None), None, None, None, None, None, None, None
+        ga = ga.contiguous()
+        require_device(ga)
+        addend = None
+        if need_x and gskip is not None:
+            addend = gskip.contiguous()
+            require_device(addend)
+        dx = torch.empty_like(x) if need_x else None
+        dgain = x.new_empty(N, C) if need_g else None
+        dbias = x.new_empty(N, C) if need_b else None
+        if dx is None and dgain is None and dbias is None:
+            return (None,) * 8
+        ws = _nz_ws(x) if (not stored or need_g or need_b) else None
+        call("slr_bn_relu_nonzero_backward", x.device, x, ga, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias,
+             int(stored), N, C, H, W, int(b8), ws, 0 if ws is None else ws.numel())
+        return dx, dgain, dbias, None, None, None, None, None
+
+
+def bn_relu_nonzero_train(x, gain, bias, *, mean=None, var=None, eps=1e-5, b8=False, fork=False):
+    """``bn_relu_mask_train`` with the per-element mask k = (x != 0) of the decoder's first block (architectures.py:369; the mask is never
+    materialised): cnt[c] = sum k + eps, mean = sum x / cnt, var = sum x^2 / cnt - mean^2 per channel (normalization.py:319-335 with a
+    [N,C,H,W] mask), a = relu(x * scale - shift) * k.  Returns (a, mean, var, msum[, x]) with msum [N,1,H,W] = sum_c k, what the partial
+    convolution behind it needs (``partial_conv3x3_counts``).  Differentiable in x, gain and bias; the gradient through the statistics
+    reaches the zero elements of x too, as the reference's autograd gives it.  mean / var, b8 and fork as ``bn_relu_mask_train``."""
+    _check_planes("bn_relu_nonzero_train", x, b8, None, (gain, bias))
+    if (mean is None) != (var is None):
+        raise ValueError("bn_relu_nonzero_train: mean and var go together")
+    if mean is not None:
+        for t in (mean, var):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
+                raise ValueError(f"bn_relu_nonzero_train: mean / var: contiguous float32 device tensors ({x.shape[1]},) required")
+        mean, var = mean.detach(), var.detach()
+    out = _BnReluNonzeroTrain.apply(x, gain, bias, mean, var, float(eps), bool(b8), bool(fork))
+    if mean is not None:
+        out = (out[0], mean, var) + tuple(out[3:])
+    return out
+
+
+def _factors_counts(msum, cin):
+    box = F.avg_pool2d(msum, 3, stride=1, padding=1, divisor_override=1)
+    um = torch.clamp(box, 0, 1)
+    return float(cin * 9) / (box + 1e-8) * um, um
+
+
+def partial_conv_factors_counts(msum, cin):
+    """``partial_conv_factors`` for a per-element mask given as its count plane ``msum`` [N,1,H,W] = sum_c mask (partialconv2d.py:61-72
+    with a [N,Cin,H,W] mask): box = conv(mask, ones) = box3x3(msum), um = clamp(box, 0, 1), ratio = 9 cin / (box + 1e-8) * um; returns
+    (r, um), r = ratio * um."""
+    _check_planes("partial_conv_factors_counts", msum, False)
+    if msum.shape[1] != 1:
+        raise ValueError(f"partial_conv_factors_counts: msum [N,1,H,W] required, got {tuple(msum.shape)}")
+    ratio, um = _factors_counts(msum, cin)
+    return ratio * um, um
+
+
+class _PartialConv3x3Counts(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xm, msum, weight, bias, owner, residual=None, in_b8=False, out_b8=False):
+        N, cin, H, W = xm.shape
+        cout = weight.shape[0]
+        buf, arith = _forward_weights(weight, owner)
+        ratio, um = _factors_counts(msum, cin)
+        out = _conv(xm, buf, arith, None, cout, (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0))
+        call("slr_pconv_train_epilogue", xm.device, out, ratio, um, bias, residual, out, N, cout, H, W, int(out_b8))
+        ctx.save_for_backward(xm, ratio, um, weight)     # (um is 0 or 1: ratio * um has ratio's bits, it is r)
+        ctx.owner, ctx.layouts = owner, (in_b8, out_b8)
+        ctx.mark_non_differentiable(um)
+        return out, um
+
+    @staticmethod
+    def backward(ctx, g, _g_um):
+        xm, r, um, weight = ctx.saved_tensors
+        owner, (in_b8, out_b8) = ctx.owner, ctx.layouts
+        g = g.contiguous()
+        require_device(g)
+        cout, cin = weight.shape[:2]
+        need_x, _, need_w, need_b = ctx.needs_input_grad[:4]
+        gx = gw = gb = None
+        glayout = GRAD_G_B8 if out_b8 else 0
+        if need_x or need_w or need_b:                   # from here on exactly _PartialConv3x3.backward
+            gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
+            if need_x:
+                buf, arith = _backward_weights(weight, owner)
+                gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
+            if need_w:
+                gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
+        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None
+
+
+def partial_conv3x3_counts(xm, msum, weight, bias, *, residual=None, in_b8=False, out_b8=False, _owner=None):
+    """``partial_conv3x3`` for a per-element mask given as its count plane: ``xm`` [N,Cin,H,W] already activated and masked, ``msum``
+    [N,1,H,W] = sum_c mask (``bn_relu_nonzero_train``'s).  A bias-free convolution on the fp32 rung, then
+    out = (raw * ratio + bias) * um (+ residual) with the factors of ``partial_conv_factors_counts``; returns (out, update_mask).
+    Differentiable in xm, weight, bias and residual."""
+    if bias is None:
+        raise ValueError("partial_conv3x3_counts: a bias is required (PartialConv2d adds it inside the mask ratio)")
+    _check("partial_conv3x3_counts", xm, weight, bias, mask=msum, in_b8=in_b8, out_b8=out_b8, residual=residual)
+    return _PartialConv3x3Counts.apply(xm, msum.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8))
+
+
+class TrainablePconvInputBlock(TrainablePconvResBlock):
+    """The decoder's first block: ``TrainablePconvResBlock`` called with the per-element mask (x != 0) (architectures.py:369).  Same
+    sub-modules and state-dict keys as its parent."""
+
+    def forward(self, x, b8_in=False, noise=None):
+        """-> (y, update_mask, b8_out); arguments as the parent's, without the mask."""
+        _check_planes("TrainablePconvInputBlock", x, b8_in)
+        cout = self.conv_aa.weight.shape[0]
+        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
+        n1, n2 = noise if noise is not None else (None, None)
+        a, _, _, msum, xs = self.bn1(x, None, n1, b8=b8_in, fork=True, nonzero=True)             # blocks.py:225-231
+        a, m = partial_conv3x3_counts(a, msum, self.conv_aa.weight, self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa)
+        a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238 -- the mask is channel-uniform from here
+        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs
+        a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)
+        if self.kind == "Up":
+            a = upsample_up(a, b8)
+        elif self.kind:
+            a = avgpool_down(a, b8)
+        return a, self.resample_mask(m), b8
+
+
+# --------------------------------------------------------------------------- the plain block and the networks
+
+class TrainableResBlock(nets.ResBlock):
+    """``nets.ResBlock`` (ResNet_Block, blocks.py:47-87) as one differentiable unit in training or eval mode: the noise-conditioned
+    batch-norm without a mask (manual_bn), two 3x3 convolutions, the 1x1 skip convolution with its bias.  Same sub-module names and
+    state-dict keys, the BNs' noise layers as extra keys."""
+
+    def __init__(self, cin, cout, resample=None):
+        super().__init__(cin, cout, resample)
+        self.bn1, self.bn2 = TrainableNoiseBN(cin), TrainableNoiseBN(cout)
+        self.conv_aa, self.conv_ab = TrainableConv3x3(cin, cout), TrainableConv3x3(cout, cout)
+        self.conv_b = TrainableConv1x1(cin, cout, bias=True) if self.conv_b is not None else None
+        self.kind = resample
+
+    def forward(self, x, b8_in=False, noise=None):
+        """-> (y, b8_out).  bn1 -> conv_aa -> bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue -> one resampling of the sum."""
+        _check_planes("TrainableResBlock", x, b8_in)
+        cout = self.conv_aa.weight.shape[0]
+        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
+        n1, n2 = noise if noise is not None else (None, None)
+        a, _, _, xs = self.bn1(x, None, n1, b8=b8_in, fork=True)                    # blocks.py:69-72
+        a = self.conv_aa(a, in_b8=b8_in, out_b8=b8)
+        a = self.bn2(a, None, n2, b8=b8)[0]                                          # :73-75
+        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs        # :78-81
+        a = self.conv_ab(a, in_b8=b8, out_b8=b8, residual=skip)                      # :87
+        if self.kind == "Up":
+            a = upsample_up(a, b8)
+        elif self.kind:
+            a = avgpool_down(a, b8)
+        return a, b8
+
+
+def _net_plan(name, first, inner, last, widths, updown, default_updown):
+    widths = list(inner if widths is None else widths)
+    updown = list(default_updown if updown is None else updown)
+    if len(updown) != len(widths) + 1:
+        raise ValueError(f"{name}: {len(widths)} inner widths need {len(widths) + 1} resampling entries, got {len(updown)}")
+    if any(u is not None and u is not False and u not in ("Down", "Up") for u in updown):
+        raise ValueError(f"{name}: updown entries are None / False, 'Down' or 'Up', got {updown}")
+    if any(not isinstance(c, int) or c < 1 for c in [first, last] + widths):
+        raise ValueError(f"{name}: channel counts are positive integers")
+    if last % 8 == 0:
+        raise ValueError(f"{name}: the net ends in NCHW; its last channel count must not be a multiple of 8, got {last}")
+    return [first] + widths + [last], [u or None for u in updown]
+
+
+def _noise_of(noise, n):
+    if noise is None:
+        return [None] * n
+    if len(noise) != n:
+        raise ValueError(f"noise: one (noise1, noise2) pair per block required, got {len(noise)} for {n} blocks")
+    return list(noise)
+
+
+class _TrainableResNet:
+    """forward of the nets made of ``TrainableResBlock``s: the blocks in order, NCHW at the end."""
+
+    def _run(self, x, noise):
+        b8 = False
+        for blk, nz in zip(self.blocks, _noise_of(noise, len(self.blocks))):
+            x, b8 = blk(x, b8, noise=nz)
+        assert not b8                                    # the few-channel end is NCHW
+        return x
+
+
+class TrainableEncoderWithZ(_TrainableResNet, nets.EncoderWithZ):
+    """``nets.EncoderWithZ`` (ResNetEncoder_with_Z, architectures.py:155-197) whose weights learn.  widths: the seven inner widths
+    (default nets._ENC[1:]); updown: the eight blocks' resampling (default none)."""
+
+    def __init__(self, cin=3, feat=64, *, widths=None, updown=None):
+        nn.Module.__init__(self)
+        n = len(nets._ENC[1:] if widths is None else widths) + 1
+        ch, ud = _net_plan("TrainableEncoderWithZ", cin, nets._ENC[1:], feat + 1, widths, updown, [None] * n)
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+
+    def forward(self, x, noise=None):
+        x = self._run(x, noise)
+        return x[:, :-1].contiguous(), x[:, -1:].contiguous()          # :195-197
+
+
+class TrainableEncoder(_TrainableResNet, nets.Encoder):
+    """``nets.Encoder`` (ResNetEncoder, architectures.py:121-153) whose weights learn; widths / updown as ``TrainableEncoderWithZ``."""
+
+    def __init__(self, cin=3, cout=2, *, widths=None, updown=None):
+        nn.Module.__init__(self)
+        n = len(nets._ENC[1:] if widths is None else widths) + 1
+        ch, ud = _net_plan("TrainableEncoder", cin, nets._ENC[1:], cout, widths, updown, [None] * n)
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+
+    def forward(self, x, noise=None):
+        return self._run(x, noise)
+
+
+class TrainableBGDecoder(_TrainableResNet, nets.BGDecoder):
+    """``nets.BGDecoder`` (ResNetBGDecoder, architectures.py:233-260) whose weights learn.  widths: the inner widths (default nets._DEC);
+    updown: the blocks' resampling (default nets._UPDOWN)."""
+
+    def __init__(self, cin=3, cout=3, *, widths=None, updown=None):
+        nn.Module.__init__(self)
+        ch, ud = _net_plan("TrainableBGDecoder", cin, nets._DEC, cout, widths, updown, nets._UPDOWN)
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+
+    def forward(self, x, noise=None):
+        return self._run(x, noise)
+
+
+class TrainableDecoderPconv2(nets.DecoderPconv2):
+    """``nets.DecoderPconv2`` (ResNetDecoderPconv2, architectures.py:345-375) whose weights learn: block 0 is a
+    ``TrainablePconvInputBlock`` (mask = x != 0, :369), the others ``TrainablePconvResBlock``s.  widths / updown as ``TrainableBGDecoder``."""
+
+    def __init__(self, cin=64, cout=3, *, widths=None, updown=None):
+        nn.Module.__init__(self)
+        ch, ud = _net_plan("TrainableDecoderPconv2", cin, nets._DEC, cout, widths, updown, nets._UPDOWN)
+        self.blocks = nn.ModuleList((TrainablePconvResBlock if i else TrainablePconvInputBlock)(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+
+    def forward(self, x, noise=None):
+        noise = _noise_of(noise, len(self.blocks))
+        x, mask, b8 = self.blocks[0](x, False, noise=noise[0])
+        for blk, nz in zip(self.blocks[1:], noise[1:]):
+            x, mask, b8 = blk(x, mask, b8, noise=nz)
+        assert not b8                                    # the 1- / 3-channel end is NCHW
+        return x
