@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 17
+#define SLR_ABI_VERSION 18
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -737,6 +737,58 @@ int slr_bn_relu_nonzero_backward(const float *x, const float *ga, const float *s
  * um = clamp(box3x3(msum), 0, 1) around a bias-free slr_conv3x3_forward. */
 int slr_pconv_train_epilogue(const float *raw0, const float *ratio, const float *um, const float *bias, const float *residual,
                              float *out, int N, int C, int H, int W, int b8, void *stream);
+
+/* ------------------------------------------------------------------ adversarial loss: the PatchGAN discriminator (ABI 18; csrc/disc.hip)
+ * What the reference's trainer (models/base_model.py:15-30, 118-151, --discriminator_losses pix2pixHD --norm_D spectralinstance) runs
+ * through models/networks/discriminators.py:78-139 (NLayerDiscriminator) in both directions.  Everything is NCHW fp32.  None of the
+ * entry points synchronises, none uses atomics: every long sum runs in a fixed order in double, the same inputs (and the same split
+ * count) give the same bits.  H, W are the sizes of the convolution's INPUT everywhere; its output is OH = H / stride + 1,
+ * OW = W / stride + 1 (kernel 4, padding 2).  Limits: stride 1 or 2, N < 65536, channels < 65536, N * H * W and N * OH * OW < 2^31. */
+
+/* Bytes of a prepared weight buffer: ceil(Cout / 32) * Cin * 2048 for the forward, ceil(Cin / 32) * Cout * 2048 for backward != 0;
+ * 0 for sizes the calls refuse. */
+size_t slr_conv4x4_weight_bytes(int Cout, int Cin, int backward);
+
+/* w [Cout,Cin,4,4] (nn.Conv2d's layout) -> MFMA fragments, each weight multiplied by scale[0] if `scale` (a DEVICE scalar: the 1 / sigma
+ * of torch.nn.utils.spectral_norm, normalization.py:105-106) is not NULL.  backward = 0: the order slr_conv4x4_forward reads;
+ * backward != 0: the order slr_conv4x4_backward_data reads for this `stride` (the forward's order does not depend on it). */
+int slr_conv4x4_f32_weights(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int stride, int backward, void *stream);
+
+/* nn.Conv2d(Cin, Cout, kernel_size=4, stride, padding=2) (discriminators.py:92, 104-110, 116): in [N,Cin,H,W] -> out [N,Cout,OH,OW],
+ * bias [Cout] or NULL, leaky != 0: nn.LeakyReLU(slope) of the result (discriminators.py:93).  Any Cin, Cout, H, W >= 1.  An implicit
+ * GEMM on v_mfma_f32_32x32x2_f32: fp32 operands, products and accumulation. */
+int slr_conv4x4_forward(const float *in, const void *wfrag, const float *bias, float *out, int N, int Cin, int Cout, int H, int W,
+                        int stride, int leaky, float slope, void *stream);
+
+/* The gradient to the input of the convolution above (what autograd's backward of F.conv2d returns for its input):
+ *   gin[n,ci,iy,ix] = sum_co sum_{ky,kx} g'[n,co,(iy+2-ky)/stride,(ix+2-kx)/stride] * w[co,ci,ky,kx] over the taps whose division is
+ * exact and in range, a gather: every element of gin [N,Cin,H,W] is stored once.  g [N,Cout,OH,OW]; g' = g, or with gate [N,Cout,OH,OW]
+ * (the LeakyReLU'd output of the forward) g' = g * (gate > 0 ? 1 : slope).  wfrag: prepared with backward = 1 and this stride. */
+int slr_conv4x4_backward_data(const float *g, const float *gate, const void *wfrag, float *gin, int N, int Cin, int Cout, int H, int W,
+                              int stride, float slope, void *stream);
+
+/* Workspace of slr_conv4x4_weight_grad in bytes: al256(S * 16 * Cout * Cin * 4), the partial sums of S slabs.  S = min(splits, chunks,
+ * 65535) for splits > 0; for splits = 0 the library's choice min(ceil(512 / channel tiles), chunks, 32 MiB / (64 Cout Cin)) (at least 1)
+ * with chunks = N * OH * ceil(OW / 32) and channel tiles = ceil(Cin / 32) * ceil(Cout / 32) (csrc/slr_tuning.hpp).  0 for sizes the
+ * call refuses. */
+size_t slr_conv4x4_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int stride, int splits);
+
+/* Weight and bias gradient of the convolution above: dw[co][ci][ky][kx] = sum_{n,oy,ox} g'[n,co,oy,ox] * x[n,ci,s*oy+ky-2,s*ox+kx-2]
+ * (zero padding), plain [Cout,Cin,4,4]; db[co] = sum g' (NULL: not wanted).  x [N,Cin,H,W], g and gate as in slr_conv4x4_backward_data.
+ * fp32 products and sums on v_mfma_f32_32x32x2_f32 inside a slab of pixels, the slabs added in double in slab order; db in double
+ * throughout.  ws: 256-byte aligned, slr_conv4x4_grad_ws_bytes bytes, else SLR_E_WORKSPACE. */
+int slr_conv4x4_weight_grad(const float *x, const float *g, const float *gate, float *dw, float *db, int N, int Cin, int Cout, int H, int W,
+                            int stride, float slope, int splits, void *ws, size_t ws_bytes, void *stream);
+
+/* nn.InstanceNorm2d(C, affine=False) + nn.LeakyReLU(slope) (normalization.py:121-128, discriminators.py:112): per (n, c) plane
+ * m = mean(x), rstd = 1 / sqrt(mean((x - m)^2) + eps), y = leaky((x - m) * rstd); mean, rstd [N*C] are kept for the backward.  Planes
+ * of at least 4 elements; the sums in double.  One workgroup per plane. */
+int slr_instnorm_lrelu_forward(const float *x, float *y, float *mean, float *rstd, int N, int C, int H, int W, float eps, float slope,
+                               void *stream);
+
+/* Its backward: xh = (x - m) * rstd, gh = gy * (xh > 0 ? 1 : slope), gx = rstd * (gh - mean(gh) - xh * mean(gh * xh)). */
+int slr_instnorm_lrelu_backward(const float *x, const float *gy, const float *mean, const float *rstd, float *gx, int N, int C, int H,
+                                int W, float slope, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 17
+ABI_VERSION = 18
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -106,6 +106,14 @@ SIGNATURES = {
     "slr_bn_relu_nonzero_train": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
     "slr_bn_relu_nonzero_backward": (_i, [_fp] * 8 + [_f] + [_fp] * 4 + [_i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_pconv_train_epilogue": (_i, [_fp] * 6 + [_i, _i, _i, _i, _i, _vp]),
+    "slr_conv4x4_weight_bytes": (_sz, [_i, _i, _i]),
+    "slr_conv4x4_f32_weights": (_i, [_fp, _fp, _vp, _i, _i, _i, _i, _vp]),
+    "slr_conv4x4_forward": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "slr_conv4x4_backward_data": (_i, [_fp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "slr_conv4x4_grad_ws_bytes": (_sz, [_i] * 7),
+    "slr_conv4x4_weight_grad": (_i, [_fp] * 5 + [_i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
+    "slr_instnorm_lrelu_forward": (_i, [_fp] * 4 + [_i, _i, _i, _i, _f, _f, _vp]),
+    "slr_instnorm_lrelu_backward": (_i, [_fp] * 5 + [_i, _i, _i, _i, _f, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 
