@@ -517,7 +517,7 @@ int slr_conv1x1_small(const float *in, const float *w, const float *bias, float 
                       int N, int Cin, int Cout, int H, int W, int in_b8 /* `in` channel-blocked; `out` is always NCHW */,
                       void *stream);
 
-/* ------------------------------------------------------------------ motion U-Nets (ABI 11; csrc/motion.hip)
+/* ------------------------------------------------------------------ motion U-Nets (ABI 11; csrc/motion.hip, csrc/conv4x4.hip)
  * The networks that predict the motion field from a still image: Unet4Motion (models/networks/architectures.py:382-493, used by
  * models/unet_motion.py:30-109) and SPADEUnet4MaskMotion (architectures.py:602-743 with SPADE, models/networks/networks.py:422-463, used by
  * unet_motion.py:111-191).  All their convolutions run on the fp32 rung (v_mfma_f32_32x32x2_f32): the 3x3 ones through
@@ -738,7 +738,7 @@ int slr_bn_relu_nonzero_backward(const float *x, const float *ga, const float *s
 int slr_pconv_train_epilogue(const float *raw0, const float *ratio, const float *um, const float *bias, const float *residual,
                              float *out, int N, int C, int H, int W, int b8, void *stream);
 
-/* ------------------------------------------------------------------ adversarial loss: the PatchGAN discriminator (ABI 18; csrc/disc.hip)
+/* ------------------------------------------------------------------ adversarial loss: the PatchGAN discriminator (ABI 18; csrc/disc.hip, csrc/conv4x4.hip)
  * What the reference's trainer (models/base_model.py:15-30, 118-151, --discriminator_losses pix2pixHD --norm_D spectralinstance) runs
  * through models/networks/discriminators.py:78-139 (NLayerDiscriminator) in both directions.  Everything is NCHW fp32.  None of the
  * entry points synchronises, none uses atomics: every long sum runs in a fixed order in double, the same inputs (and the same split

@@ -245,7 +245,6 @@ __global__ __launch_bounds__(BG_THREADS) void bn_backward_dx_kernel(const float 
 // 32 x 32 accumulators) over a slab of the pixels, in chunks of 32 consecutive pixels of one image: at 64 -> 128 channels one workgroup
 // column covers the whole weight, so X and G are read from HBM exactly once.  Staged tiles are [32-channel tile][pixel][channel] as in
 // conv_grad.hip (pixel stride 32 blocked / 33 NCHW); the next chunk's loads are in flight while the matrix pipe works on this one.
-typedef float bg_f16v __attribute__((ext_vector_type(16)));
 constexpr int W1_P = 32, W1_CO = 128, W1_CI = 64;
 constexpr int w1_stride(bool b8) { return b8 ? 32 : 33; }
 
@@ -321,7 +320,7 @@ __global__ __launch_bounds__(BG_THREADS) void conv1x1_wgrad_kernel(const float *
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
     const float *ga = gs + (wave * W1_P + h) * PSG + c;
     const float *xa = xs + h * PSX + c;
-    bg_f16v acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(BG_THREADS) void conv1x1_wgrad_kernel(const float *
         if (ci < Cin)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = co0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int co = co0 + wave * 32 + mfma32_row(r, h);
                 if (co < Cout) part[((size_t)s * Cout + co) * Cin + ci] = acc[j][r];
             }
     }

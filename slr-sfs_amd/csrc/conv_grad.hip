@@ -16,7 +16,6 @@
 
 namespace slr {
 
-typedef float wg_f16v __attribute__((ext_vector_type(16)));
 
 constexpr int WG_THREADS = 256;
 constexpr int WG_TC = 64;                              // channels of G and of X per workgroup (two 32-channel MFMA tiles each)
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_wgrad_kernel(const floa
     const int c = lane & 31, h = lane >> 5;
     const float *ga = gs + tco * WG_GPIX * PSG + h * PSG + c;
     const float *xa = xs + tci * WG_XPIX * PSX + h * PSX + c;
-    wg_f16v acc[9];
+    f32x16 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_wgrad_kernel(const floa
         for (int t = 0; t < 9; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = co0 + tco * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int co = co0 + tco * 32 + mfma32_row(r, h);
                 if (co < Cout) part[(((size_t)s * 9 + t) * Cout + co) * Cin + ci] = acc[t][r];
             }
     }

@@ -49,6 +49,12 @@ constexpr int SEG_TWO  = SLR_EPT_TWO * TILE_PIX;   // segment length, forward+ba
 
 inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// ---- the 32x32 fp32 MFMA result ------------------------------------------------------------
+// The C/D operand of v_mfma_f32_32x32x2_f32: 16 registers per lane; the column is lane & 31, register r of lane half `half` = lane >> 5
+// holds row mfma32_row(r, half).
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__host__ __device__ constexpr int mfma32_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
 // ---- bilinear footprint ------------------------------------------------------------------
 // Restates models/softsplat.py:169-184 (target coordinate, NW corner, 4 weights).
 struct Corners {

@@ -790,7 +790,7 @@ def load_reference_state_dict(net, sd, prefix):
 # --------------------------------------------------------------------------- motion U-Nets (still image -> motion field)
 # Unet4Motion (models/networks/architectures.py:382-493) and SPADEUnet4MaskMotion (:602-743 with SPADE, models/networks/networks.py:422-463),
 # the motion predictors of models/unet_motion.py:30-191.  On a device every stage is one of this package's kernels and every convolution runs
-# on the fp32 rung (v_mfma_f32_32x32x2_f32): the 4x4 / stride 2 encoder convolutions on slr_conv4x4s2_forward (csrc/motion.hip), the 3x3
+# on the fp32 rung (v_mfma_f32_32x32x2_f32): the 4x4 / stride 2 encoder convolutions on slr_conv4x4s2_forward (csrc/conv4x4.hip), the 3x3
 # ones on slr_conv3x3_forward with SLR_CONV_F32 (direct, not Winograd).  The predicted field feeds the Euler integration, which rounds
 # positions at every step: a perturbation of the motion moves whole trajectories, so no reduced-precision rung is offered here.
 MOTION_GRID = 256                        # eight stride-2 halvings: H and W must be multiples of 256 (the reference fails in torch.cat otherwise)

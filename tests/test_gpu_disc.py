@@ -110,7 +110,7 @@ def test_convolution_forward_backward_data_weight_gradient(S, shape):
                 assert torch.equal(db, seen.setdefault("db", db)), tag
 
 
-# The launch rule of csrc/disc.hip (dc_launch) takes 2 or 4 tiles of 32 produced channels per workgroup once the launch has 512
+# The launch rule of csrc/conv4x4.hip (c4_launch) takes 2 or 4 tiles of 32 produced channels per workgroup once the launch has 512
 # workgroups; the shapes above are all below that.  One cheap shape per mode and tile count: the forward produces Cout, the backward-data
 # Cin; the pixel tiles are those of the output (forward), of the input (stride-1 backward) or of its largest parity class (stride 2).
 PATH_SHAPES = {(1, 8, 128, 128, 128, 1): ("forward", 4), (1, 8, 64, 128, 128, 1): ("forward", 2), (1, 128, 8, 128, 128, 1): ("backward", 4),

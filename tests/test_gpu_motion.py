@@ -62,6 +62,74 @@ def test_conv4x4s2_vs_fp64(S, n, cin, cout, oh, ow, leaky, bn):
     assert err <= 2e-6 * max(ref.abs().max().item(), 1.0), err
 
 
+# The encoder convolution and the discriminator's stride-2 forward are one kernel body (csrc/conv4x4.hip): a zero row on top and a zero
+# column on the left turn the pad-1 taps of output o into the pad-2 taps of output o + 1, so the two entry points give the same bits
+# wherever their launches take the same CT (tiles of 32 output channels per workgroup) and KW (waves splitting the input channels).
+SAME_BITS = {(2, 3, 8, 2, 2): (1, 2), (1, 5, 40, 9, 6): (1, 4), (1, 33, 70, 7, 11): (1, 16), (2, 256, 32, 12, 12): (1, 16),
+             (1, 8, 64, 256, 256): (2, 4), (1, 8, 128, 256, 256): (4, 4)}        # (N, Cin, Cout, H, W): (CT, KW)
+
+
+def _launch_rule(cout, pixels, cin):
+    """(CT, KW) of c4_launch in csrc/conv4x4.hip for a forward launch."""
+    ntile, ptiles = (cout + 31) // 32, (pixels + 31) // 32
+    ct = 4 if ntile % 4 == 0 else 2 if ntile % 2 == 0 else 1
+    if ptiles * (ntile // ct) < 512:
+        ct = 1
+    wgs, kw = ptiles * (ntile // ct), 1
+    while kw < 16 // ct and wgs * kw < 2048 and 2 * kw <= cin:
+        kw *= 2
+    return ct, kw
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _both_entry_points(S, shape, leaky=None):
+    n, cin, cout, h, w = shape
+    g = torch.Generator().manual_seed(cin * 1000 + cout + h)
+    x = _dev(torch.randn(n, cin, h, w, generator=g))
+    conv = S.nets.Conv4x4s2(cin, cout)
+    conv.weight.data.copy_(torch.randn(cout, cin, 4, 4, generator=g) / (cin * 16) ** 0.5)
+    conv.bias.data.copy_(torch.randn(cout, generator=g) * 0.1)
+    conv = conv.cuda()
+    oh, ow = (h - 2) // 2 + 1, (w - 2) // 2 + 1
+    with torch.no_grad():
+        motion = conv(x, leaky=leaky)
+        xp = F.pad(x, (1, 0, 1, 0))
+        disc = S.conv4x4(xp if leaky is None else F.leaky_relu(xp, leaky), conv.weight, conv.bias, stride=2)[:, :, 1:1 + oh, 1:1 + ow]
+    assert motion.shape == disc.shape == (n, cout, oh, ow)
+    return conv, x, motion, disc
+
+
+@pytest.mark.parametrize("shape", sorted(SAME_BITS), ids=lambda s: "x".join(map(str, s)))
+def test_conv4x4s2_and_the_discriminator_forward_give_the_same_bits(S, shape):
+    n, cin, cout, h, w = shape
+    pair = SAME_BITS[shape]
+    assert _launch_rule(cout, n * ((h - 2) // 2 + 1) * ((w - 2) // 2 + 1), cin) == pair
+    assert _launch_rule(cout, n * ((h + 1) // 2 + 1) * ((w + 1) // 2 + 1), cin) == pair
+    conv, x, motion, disc = _both_entry_points(S, shape)
+    assert torch.equal(_bits(motion), _bits(disc))
+    if shape != (1, 33, 70, 7, 11):
+        return
+    # the LeakyReLU of the value read is the LeakyReLU of the input
+    _, _, motion_leaky, disc_leaky = _both_entry_points(S, shape, leaky=0.2)
+    assert torch.equal(_bits(motion_leaky), _bits(disc_leaky)) and not torch.equal(motion_leaky, motion)
+    # the affine epilogue is a multiply, then an add, of the plain result
+    g = torch.Generator().manual_seed(7)
+    bn = S.nets.EvalBN(cout)
+    bn.running_mean.copy_(torch.randn(cout, generator=g) * 0.2)
+    bn.running_var.copy_(torch.rand(cout, generator=g) + 0.5)
+    bn.weight.copy_(1 + 0.1 * torch.randn(cout, generator=g))
+    bn.bias.copy_(0.1 * torch.randn(cout, generator=g))
+    bn = bn.cuda()
+    with torch.no_grad():
+        scale, shift = bn.scale_shift()
+        fused = conv(x, bn=bn)
+        unfused = motion * scale[None, :, None, None] + shift[None, :, None, None]
+    assert torch.equal(_bits(fused), _bits(unfused))
+
+
 @pytest.mark.parametrize("n,c,h,w", [(1, 32, 96, 64), (2, 256, 3, 3), (1, 64, 2, 4), (1, 128, 48, 48)])
 def test_instnorm_spade_vs_fp64(S, n, c, h, w):
     g = torch.Generator().manual_seed(c + h)
