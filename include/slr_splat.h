@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 18
+#define SLR_ABI_VERSION 19
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -789,6 +789,50 @@ int slr_instnorm_lrelu_forward(const float *x, float *y, float *mean, float *rst
 /* Its backward: xh = (x - m) * rstd, gh = gy * (xh > 0 ? 1 : slope), gx = rstd * (gh - mean(gh) - xh * mean(gh * xh)). */
 int slr_instnorm_lrelu_backward(const float *x, const float *gy, const float *mean, const float *rstd, float *gx, int N, int C, int H,
                                 int W, float slope, void *stream);
+
+/* ------------------------------------------------------------------ optimiser step: multi-tensor Adam (ABI 19; csrc/adam.hip)
+ * torch.optim.Adam(params, lr, betas, eps) with no weight decay and no amsgrad -- the two optimisers of the reference's trainer
+ * (models/base_model.py:21-37) -- over any number of fp32 tensors in at most two launches.  A PLAN in device memory describes the
+ * tensors; it is built on the host (the two entry points below touch no device) and uploaded by the caller with one copy.
+ *
+ * Plan layout (little endian; offsets in bytes from the plan's start, which is 16-byte aligned):
+ *   header, 64 bytes:   uint32 magic = SLR_ADAM_PLAN_MAGIC, uint32 chunk = SLR_ADAM_CHUNK, uint32 n_tensors, uint32 n_work,
+ *                       uint64 tensors_off = 64, uint64 work_off, uint64 scratch_off, uint64 bytes, 16 bytes of zeros
+ *   tensors_off:        n_tensors records of 48 bytes: uint64 p, g, m, v, step (device addresses; step: the tensor's fp32 step counter),
+ *                       int64 numel
+ *   work_off:           n_work records of 16 bytes: int32 tensor, int32 count, int64 start -- elements [start, start + count) of that
+ *                       tensor, start a multiple of SLR_ADAM_CHUNK, 1 <= count <= SLR_ADAM_CHUNK; the records of a tensor follow each
+ *                       other in order of start and cover [0, numel) exactly once; a tensor with numel = 0 has none
+ *   scratch_off:        n_tensors pairs of fp32, written by every step: 1 - beta1^step and sqrt(1 - beta2^step)
+ *   work_off = align16(64 + 48 n_tensors), scratch_off = align16(work_off + 16 n_work), bytes = align256(scratch_off + 8 n_tensors).
+ * The update kernel takes one work item per workgroup and loop trip: the plan is data, never kernel arguments, so n_tensors has no limit. */
+#define SLR_ADAM_CHUNK      4096
+#define SLR_ADAM_PLAN_MAGIC 0x4d414441u   /* "ADAM" */
+#define SLR_ADAM_ZERO_GRADS 1             /* flags bit 0: write zeros to g after reading it (zero_grad with fixed gradient pointers) */
+
+/* Bytes of the plan of n tensors with numel[t] elements (host arithmetic only); 0 for n <= 0, a negative numel or 2^31 work items. */
+size_t slr_adam_plan_bytes(int n, const long long *numel);
+
+/* Writes the plan into CALLER memory `host_buf` of `bytes` >= slr_adam_plan_bytes(n, numel) bytes (host only; nothing touches a device).
+ * p, g, m, v, step: n device addresses each, as integers, 4-byte aligned; numel[t] = 0 is legal and costs nothing (its step still
+ * advances).  The header's n_work is the value slr_adam_step wants. */
+int slr_adam_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *p, const unsigned long long *g,
+                       const unsigned long long *m, const unsigned long long *v, const unsigned long long *step, const long long *numel);
+
+/* One Adam step of every tensor of the plan (a copy of a filled plan in device memory, 16-byte aligned), in torch's arithmetic and order,
+ * fp32 with single roundings:
+ *     step += 1;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),  bc = 1 - beta^step
+ * Launch (a), one workgroup: per tensor the step counter and the two corrections, evaluated in double, into the plan's scratch table.
+ * Launch (b): the update -- 16-byte accesses of all four streams where a tensor's four pointers are 16-byte aligned, scalar ones
+ * otherwise; a capped grid strides over the work items; no atomics; every element is read and written by exactly one thread, so the bits
+ * depend neither on the grid nor on how tensors are grouped into plans.
+ *   lr_dev   a DEVICE fp32 scalar: a new learning rate needs no new plan and cannot break a captured graph
+ *   betas    HOST, two doubles (beta1, beta2), each in [0, 1): read before the call returns.  Doubles because 1 - beta is: the fp32
+ *            nearest to 0.999 is 0.99900001287, and 1 - that is off by 1.3e-5 of itself -- in v and in the second correction alike
+ *   eps      > 0
+ *   flags    SLR_ADAM_ZERO_GRADS or 0; any other bit is refused
+ * Argument errors return SLR_E_BADARG before anything is launched. */
+int slr_adam_step(void *plan_dev, int n_tensors, int n_work, const float *lr_dev, const double *betas, float eps, int flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 18
+ABI_VERSION = 19
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -114,6 +114,9 @@ SIGNATURES = {
     "slr_conv4x4_weight_grad": (_i, [_fp] * 5 + [_i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "slr_instnorm_lrelu_forward": (_i, [_fp] * 4 + [_i, _i, _i, _i, _f, _f, _vp]),
     "slr_instnorm_lrelu_backward": (_i, [_fp] * 5 + [_i, _i, _i, _i, _f, _vp]),
+    "slr_adam_plan_bytes": (_sz, [_i, _vp]),
+    "slr_adam_plan_fill": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slr_adam_step": (_i, [_vp, _i, _i, _fp, _vp, _f, _i, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 
