@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 19
+#define SLR_ABI_VERSION 20
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -833,6 +833,92 @@ int slr_adam_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long 
  *   flags    SLR_ADAM_ZERO_GRADS or 0; any other bit is refused
  * Argument errors return SLR_E_BADARG before anything is launched. */
 int slr_adam_step(void *plan_dev, int n_tensors, int n_work, const float *lr_dev, const double *betas, float eps, int flags, void *stream);
+
+/* ------------------------------------------------------------------ spectral normalisation of the generator (ABI 20; csrc/spectral.hip, csrc/conv.hip)
+ * torch.nn.utils.spectral_norm as the reference wraps it around every 3x3, partial 3x3 and 1x1 convolution of the generator
+ * (models/layers/blocks.py:5-35, models/networks/architectures.py:18-66) and around the bias-free nn.Linear maps of the noise layers
+ * (models/layers/normalization.py:6-16) under --norm_G sync:spectral_batch, the option of every training script it ships: the parameter is
+ * weight_orig, the buffers weight_u / weight_v, the effective weight weight_orig / sigma.  None of the entry points synchronises, none uses
+ * atomics; every long sum is accumulated in double in an order the matrix's own shape fixes: the same bits from run to run and whatever
+ * else is in the list.
+ *
+ * Plan of slr_spectral_sigma (little endian; offsets in bytes from the plan's start, which is 16-byte aligned):
+ *   header, 64 bytes:   uint32 magic = SLR_SPECTRAL_PLAN_MAGIC, uint32 max_dim = SLR_SPECTRAL_MAX_DIM, uint32 n_tensors, uint32 n_work,
+ *                       uint64 tensors_off = 64, uint64 bytes, uint64 total_u (sum of rows), uint64 total_v (sum of cols),
+ *                       uint64 work_off, uint64 scratch_off
+ *   tensors_off:        n_tensors records of 64 bytes: uint64 w, u, v (device addresses), int32 rows, int32 cols, int32 slot (= the
+ *                       record's index: its element of inv_sigma), int32 bands, int64 u_off, int64 v_off (elements into the saved
+ *                       arrays: the running sums of rows / cols), int64 scratch (bytes from the plan's start; 0 where bands = 0)
+ *   work_off:           n_work records of 8 bytes: int32 tensor, int32 band -- one per band of every banded matrix, in order
+ *   scratch_off:        per banded matrix align256(8 (bands cols + rows)) bytes, written by every call: the bands' partial W^T u
+ *                       [bands][cols] and W v [rows] in double
+ *   A matrix is BANDED when rows cols >= SLR_SPECTRAL_SPLIT_ELEMENTS and rows >= 2 SLR_SPECTRAL_BAND_ROWS: bands =
+ *   ceil(rows / SLR_SPECTRAL_BAND_ROWS), band b holds rows [b, b + 1) SLR_SPECTRAL_BAND_ROWS; bands = 0 otherwise.
+ *   work_off = align16(64 + 64 n_tensors), scratch_off = align256(work_off + 8 n_work), bytes = align256(scratch_off + scratch).
+ * The plan is data, never kernel arguments, so n_tensors has no limit.  The scratch belongs to the plan: calls that share a plan run
+ * on one stream. */
+#define SLR_SPECTRAL_PLAN_MAGIC 0x43455053u   /* "SPEC" */
+#define SLR_SPECTRAL_MAX_DIM    3072          /* rows and cols of one matrix (the generator's largest: 256 x 2304) */
+#define SLR_SPECTRAL_GRAD_CHUNK 4096          /* elements per workgroup of slr_spectral_weight_grad */
+#define SLR_SPECTRAL_BAND_ROWS  16            /* rows per band of a banded matrix */
+#define SLR_SPECTRAL_SPLIT_ELEMENTS 32768     /* matrices of at least this many elements are banded */
+
+/* Bytes of the plan of n matrices of rows[t] x cols[t] (host arithmetic only); 0 for n <= 0 or a size outside 1 .. SLR_SPECTRAL_MAX_DIM. */
+size_t slr_spectral_plan_bytes(int n, const int *rows, const int *cols);
+
+/* Writes the plan into CALLER memory `host_buf` of `bytes` >= slr_spectral_plan_bytes(n, rows, cols) bytes (host only; nothing touches a device).
+ * w, u, v: n device addresses each, as integers, 4-byte aligned (16-byte alignment of w is used where it is there): w [rows, cols] is
+ * weight_orig viewed as [Cout, Cin k k] (spectral_norm's weight_mat, dim 0) or the [C, noise_sz] weight of a linear; u [rows], v [cols]. */
+int slr_spectral_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *w, const unsigned long long *u,
+                           const unsigned long long *v, const int *rows, const int *cols);
+
+/* SpectralNorm.compute_weight (torch/nn/utils/spectral_norm.py, n_power_iterations = 1, eps = 1e-12) of every matrix of the plan (a copy
+ * of a filled plan in device memory; n_work: the header's), a workgroup per matrix in one launch, preceded by two launches (one in eval
+ * mode) over the bands of the banded matrices where there are any -- at most three launches, whatever the list:
+ *   training != 0:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps), written in place into the buffers;
+ *   training == 0:  u and v are read only;
+ *   both:           inv_sigma[slot] = 1 / (u^T W v);  saved_u [total_u] and saved_v [total_v] receive copies of u and v at u_off / v_off:
+ *                   the constants the backward of THIS forward needs (slr_spectral_weight_grad) -- per call, not per module.
+ * Banded matrices: every band's partial W^T u over its rows in order, the partials added in band order, W v per row as elsewhere: the
+ * order of every sum is fixed by (rows, cols) alone.  A zero matrix gives a non-finite inv_sigma, as torch does. */
+int slr_spectral_sigma(void *plan_dev, int n_tensors, int n_work, float *inv_sigma, float *saved_u, float *saved_v, int training, void *stream);
+
+/* slr_conv3x3_f32_weights / slr_conv1x1_f32_weights of w * scale[0] (scale: a DEVICE scalar, the inv_sigma above; one fp32 product per
+ * weight), w [Cout,Cin,k,k] = weight_orig.  backward = 0: the buffer of the forward convolution (slr_conv*_weight_bytes(Cout, Cin) bytes),
+ * bit-equal to the unscaled entry applied to w * scale.  backward != 0: the buffer of the backward-data convolution, Cout -> Cin channels
+ * (slr_conv*_weight_bytes(Cin, Cout) bytes), read straight from weight_orig: bit-equal to the unscaled entry applied to
+ * (w * scale).flip(2, 3).transpose(0, 1).contiguous(). */
+int slr_conv3x3_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream);
+int slr_conv1x1_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream);
+
+/* The same for every convolution of a network in ONE launch, from a plan in device memory:
+ *   header, 64 bytes:   uint32 magic = SLR_CONV_PREP_PLAN_MAGIC, uint32 chunk = SLR_CONV_PREP_CHUNK, uint32 n_tensors, uint32 n_work,
+ *                       uint64 tensors_off = 64, uint64 work_off, uint64 bytes, 24 bytes of zeros
+ *   tensors_off:        n_tensors records of 48 bytes: uint64 w, uint64 wfrag, int32 slot (the element of `scales` that multiplies it),
+ *                       int32 Cout', Cin' (of the convolution the buffer serves: swapped for backward), int32 Cin' padded to 16,
+ *                       int32 taps (9 or 1), int32 backward, int32 few (the plain layout of 3x3 layers with Cout' <= 4), int32 elements
+ *   work_off:           n_work records of 8 bytes: int32 tensor, int32 start -- buffer elements [start, start + chunk) of that tensor
+ *   work_off = align16(64 + 48 n_tensors), bytes = align256(work_off + 8 n_work).
+ * cout, cin, taps, backward: n ints each, cout / cin the shape of weight_orig as in the single-tensor entries. */
+#define SLR_CONV_PREP_PLAN_MAGIC 0x50455250u   /* "PREP" */
+#define SLR_CONV_PREP_CHUNK      4096
+size_t slr_conv_prep_plan_bytes(int n, const int *cout, const int *cin, const int *taps, const int *backward);
+int slr_conv_prep_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *w, const unsigned long long *wfrag,
+                            const int *slot, const int *cout, const int *cin, const int *taps, const int *backward);
+int slr_conv_prep_scaled_multi(const void *plan_dev, int n_tensors, int n_work, const float *scales, void *stream);
+
+/* Workspace of slr_spectral_weight_grad in bytes: align256(8 * ceil(rows * cols / SLR_SPECTRAL_GRAD_CHUNK)); 0 for sizes it refuses. */
+size_t slr_spectral_grad_ws_bytes(int rows, int cols);
+
+/* The gradient to weight_orig that autograd returns through spectral_norm's weight = weight_orig / sigma, sigma = u^T W v with u and v
+ * constants (spectral_norm.py: they are detached):
+ *     out = (dw - <dw, W_eff> u v^T) * inv_sigma,   W_eff = w * inv_sigma
+ * dw [rows, cols]: the gradient at the effective weight (what the weight-gradient kernels produce); w = weight_orig; u [rows], v [cols],
+ * inv_sigma [1]: the saved values of that forward.  Two launches: partial sums of <dw, w> per chunk of SLR_SPECTRAL_GRAD_CHUNK elements
+ * in double, then the update, every workgroup adding the partials in chunk order.  The same entry serves the [C, noise_sz] linears.
+ * out may be dw.  ws: 16-byte aligned, slr_spectral_grad_ws_bytes bytes, else SLR_E_WORKSPACE. */
+int slr_spectral_weight_grad(const float *dw, const float *w, const float *u, const float *v, const float *inv_sigma, float *out,
+                             int rows, int cols, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ GPU (so the build can be checked), but every operator raises if the library is m
 tensors are not on a ROCm device.
 """
 from . import _lib  # noqa: F401
-from . import softsplat, euler_integration_manipulator, synthesis, nets, pipeline, parallel, io, motion, metrics, evaluation, training, losses, trainable, adversarial, optim  # noqa: F401
+from . import softsplat, euler_integration_manipulator, synthesis, nets, pipeline, parallel, io, motion, metrics, evaluation, training, losses, trainable, adversarial, optim, spectral  # noqa: F401
 from .training import splat_blend, TrainingSynthesis  # noqa: F401
 from .losses import SynthesisLoss, PerceptualLoss, L1LossWrapper, VGG19Features, load_vgg19_state_dict  # noqa: F401
 from .trainable import conv3x3, partial_conv3x3, TrainableConv3x3, TrainablePartialConv3x3  # noqa: F401
@@ -22,6 +22,7 @@ from .trainable import (bn_relu_nonzero_train, partial_conv_factors_counts, part
 from .adversarial import (conv4x4, instnorm_lrelu, spectral_weight, TrainableNLayerDiscriminator,  # noqa: F401
                           TrainableMultiscaleDiscriminator, GANLoss, DiscriminatorLoss)
 from .optim import Adam, TrainingOptimizers  # noqa: F401
+from .spectral import SpectralGroup, SpectralLinear, spectral_sigma, prepare_scaled, spectral_weight_grad, load_spectral_state_dict, reference_state_dict  # noqa: F401
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401
 from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all  # noqa: F401
 from .dropin import install_into_reference  # noqa: F401

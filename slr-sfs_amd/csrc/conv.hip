@@ -34,6 +34,8 @@
 //     accumulator register a pair of 128-byte row segments of the NCHW output.
 #include "slr_common.hpp"
 
+#include <string.h>
+
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -1117,18 +1119,23 @@ __global__ __launch_bounds__(256) void conv_split_weights_kernel(const float *__
 // [co tile][chunk of 16 ci][tap][lane 64][k pair 8], lane = (co & 31) + 32 * g, and the lane's k-th value is input channel
 // chunk * 16 + (pair8 ? 8 * g + k : 2 * k + g): the 3x3 kernel pairs channels (2k, 2k + 1) (its LDS rows), the 1x1 kernel (k, 8 + k)
 // (what its 8 plane loads per lane deliver).  Same bytes as the split-f16 buffer.
-__global__ __launch_bounds__(256) void conv_f32_weights_kernel(const float *__restrict__ w, float *__restrict__ wf, int Cout, int Cin,
-                                                               int CoutP, int CinP, int taps, int pair8) {
-    const int total = CoutP * CinP * taps;
+// Element i of that buffer; `scale` and `backward` as conv_weight_source (conv_few.hpp).
+__device__ __forceinline__ void conv_f32_weights_item(int i, const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ wf,
+                                                      int Cout, int Cin, int CinP, int taps, int pair8, int backward) {
     const int nchunk = CinP >> 4;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int tap = i % taps, ci = (i / taps) % CinP, co = i / (taps * CinP);
-        const float x = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * taps + tap] : 0.0f;
-        const int cl = ci & 15;
-        const int g = pair8 ? cl >> 3 : cl & 1, k = pair8 ? cl & 7 : cl >> 1;
-        const size_t frag = ((size_t)(co >> 5) * nchunk + (ci >> 4)) * taps + tap;
-        wf[frag * 512 + ((co & 31) + 32 * g) * 8 + k] = x;
-    }
+    const int tap = i % taps, ci = (i / taps) % CinP, co = i / (taps * CinP);
+    const float x = (co < Cout && ci < Cin) ? conv_weight_source(w, scale, co, ci, tap, Cout, Cin, taps, backward) : 0.0f;
+    const int cl = ci & 15;
+    const int g = pair8 ? cl >> 3 : cl & 1, k = pair8 ? cl & 7 : cl >> 1;
+    const size_t frag = ((size_t)(co >> 5) * nchunk + (ci >> 4)) * taps + tap;
+    wf[frag * 512 + ((co & 31) + 32 * g) * 8 + k] = x;
+}
+
+__global__ __launch_bounds__(256) void conv_f32_weights_kernel(const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ wf,
+                                                               int Cout, int Cin, int CoutP, int CinP, int taps, int pair8, int backward) {
+    const int total = CoutP * CinP * taps;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256)
+        conv_f32_weights_item(i, w, scale, wf, Cout, Cin, CinP, taps, pair8, backward);
 }
 
 // Saturation counter of the split-f16 kernels, ONE PER DEVICE (lazily allocated, zeroed; shared by every stream and host
@@ -1259,7 +1266,10 @@ SLR_EXPORT size_t slr_conv3x3_wino_weight_bytes(int Cout, int Cin) {
 // WWINO fp32 values in the Winograd domain (3x3 only); taps 9 (3x3) or 1 (1x1).  Cout <= 4 3x3 layers hold plain fp32 weights
 // [ci padded to 8][tap][4] on either rung (conv_few.hpp); they fit the split layout's bytes.
 enum WeightForm { WSPLIT, WF32, WWINO };
-static int conv_weights(WeightForm form, int taps, const float *w, void *buf, int Cout, int Cin, float wscale, void *stream) {
+// Cout, Cin: of the convolution the buffer serves.  scale (a device scalar or none) and backward (the source is the forward's weight
+// [Cin,Cout,k,k], read flipped and transposed): the fp32 rung only.
+static int conv_weights(WeightForm form, int taps, const float *w, void *buf, int Cout, int Cin, float wscale, void *stream,
+                        const float *scale = nullptr, int backward = 0) {
     static_assert(36 * sizeof(float) * 8 <= 32 * 16 * 9 * 2 * sizeof(_Float16), "8 input channels of plain weights fit 16 of the split layout");
     SLR_CHECK_ARG(w && buf, "null pointer");
     const int CoutP = form == WWINO ? wino_cout_pad(Cout) : taps == 9 ? conv_cout_pad(Cout) : conv1x1_cout_pad(Cout), CinP = conv_cin_pad(Cin);
@@ -1269,16 +1279,136 @@ static int conv_weights(WeightForm form, int taps, const float *w, void *buf, in
     const int total = form == WWINO ? CoutP * CinP : CoutP * CinP * taps;
     if (form != WWINO && taps == 9 && Cout <= CF_MAXCO) {
         const int CinF = conv_few_cin_pad(Cin);
-        hipLaunchKernelGGL(conv_few_weights_kernel, dim3((CinF * 36 + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CinF);
+        hipLaunchKernelGGL(conv_few_weights_kernel, dim3((CinF * 36 + 255) / 256), dim3(256), 0, st, w, scale, (float *)buf, Cout, Cin, CinF,
+                           backward);
     } else if (form == WSPLIT) {
         hipLaunchKernelGGL(conv_split_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (_Float16 *)buf, Cout, Cin, CoutP, CinP,
                            taps, wscale);
     } else if (form == WF32) {
-        hipLaunchKernelGGL(conv_f32_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CoutP, CinP,
-                           taps, taps == 1 ? 1 : 0);
+        hipLaunchKernelGGL(conv_f32_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, scale, (float *)buf, Cout, Cin, CoutP, CinP,
+                           taps, taps == 1 ? 1 : 0, backward);
     } else {
         hipLaunchKernelGGL(conv_wino_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CoutP, CinP);
     }
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- scaled preparation of the fp32 rung (ABI 20): one tensor, or every convolution of a network from a plan in device memory ----------
+
+static int conv_weights_scaled(int taps, const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
+    SLR_CHECK_ARG(scale, "null pointer (scale)");
+    SLR_CHECK_ARG(!(((uintptr_t)w | (uintptr_t)scale | (uintptr_t)wfrag) & 3), "4-byte aligned tensors");
+    return backward ? conv_weights(WF32, taps, w, wfrag, Cin, Cout, 1.0f, stream, scale, 1)
+                    : conv_weights(WF32, taps, w, wfrag, Cout, Cin, 1.0f, stream, scale, 0);
+}
+
+SLR_EXPORT int slr_conv3x3_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
+    return conv_weights_scaled(9, w, scale, wfrag, Cout, Cin, backward, stream);
+}
+
+SLR_EXPORT int slr_conv1x1_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
+    return conv_weights_scaled(1, w, scale, wfrag, Cout, Cin, backward, stream);
+}
+
+namespace slr {
+
+constexpr int PREP_CHUNK = SLR_CONV_PREP_CHUNK;        // buffer elements per work item (include/slr_splat.h)
+constexpr int PREP_MAX_GRID = 2048;
+constexpr size_t PREP_HEADER = 64;
+
+struct PrepTensor {                                    // 48 bytes: Cout, Cin of the convolution the buffer serves
+    const float *w;
+    float *wf;
+    int slot, Cout, Cin, CinP, taps, backward, few, total;
+};
+struct PrepWork {                                      // 8 bytes
+    int tensor, start;
+};
+static_assert(sizeof(PrepTensor) == 48 && sizeof(PrepWork) == 8, "the documented plan layout");
+
+inline size_t prep_work_off(int n) { return (PREP_HEADER + (size_t)n * sizeof(PrepTensor) + 15) & ~(size_t)15; }
+inline size_t prep_total(int n, long long n_work) { return al256(prep_work_off(n) + (size_t)n_work * sizeof(PrepWork)); }
+
+// elements of the buffer of one convolution (what the single-tensor kernels loop over), or -1 where the entry points refuse it
+static long long prep_elements(int Cout, int Cin, int taps, int backward) {
+    if (Cout <= 0 || Cin <= 0 || (taps != 9 && taps != 1)) return -1;
+    const int co = backward ? Cin : Cout, ci = backward ? Cout : Cin;
+    if (taps == 9 && co <= CF_MAXCO) return (long long)conv_few_cin_pad(ci) * 36;
+    const long long total = (long long)(taps == 9 ? conv_cout_pad(co) : conv1x1_cout_pad(co)) * conv_cin_pad(ci) * taps;
+    return total < (1LL << 30) ? total : -1;
+}
+
+static long long prep_count_work(int n, const int *cout, const int *cin, const int *taps, const int *backward) {
+    if (n <= 0 || !cout || !cin || !taps || !backward) return -1;
+    long long work = 0;
+    for (int t = 0; t < n; ++t) {
+        const long long e = prep_elements(cout[t], cin[t], taps[t], backward[t]);
+        if (e < 0) return -1;
+        work += (e + PREP_CHUNK - 1) / PREP_CHUNK;
+    }
+    return work < (1LL << 31) ? work : -1;
+}
+
+__global__ __launch_bounds__(256) void conv_weights_plan_kernel(const PrepTensor *__restrict__ tens, const PrepWork *__restrict__ work, int n_work,
+                                                                const float *__restrict__ scales) {
+    for (int wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
+        const PrepWork wk = work[wi];
+        const PrepTensor t = tens[wk.tensor];
+        const float *scale = scales + t.slot;
+        const int end = wk.start + PREP_CHUNK < t.total ? wk.start + PREP_CHUNK : t.total;
+        for (int i = wk.start + threadIdx.x; i < end; i += 256) {
+            if (t.few) conv_few_weights_item(i, t.w, scale, t.wf, t.Cout, t.Cin, t.backward);
+            else conv_f32_weights_item(i, t.w, scale, t.wf, t.Cout, t.Cin, t.CinP, t.taps, t.taps == 1, t.backward);
+        }
+    }
+}
+
+}  // namespace slr
+
+SLR_EXPORT size_t slr_conv_prep_plan_bytes(int n, const int *cout, const int *cin, const int *taps, const int *backward) {
+    const long long work = prep_count_work(n, cout, cin, taps, backward);
+    return work < 0 ? 0 : prep_total(n, work);
+}
+
+SLR_EXPORT int slr_conv_prep_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *w, const unsigned long long *wfrag,
+                                       const int *slot, const int *cout, const int *cin, const int *taps, const int *backward) {
+    SLR_CHECK_ARG(n > 0, "n (at least one tensor)");
+    SLR_CHECK_ARG(host_buf && w && wfrag && slot && cout && cin && taps && backward, "null pointer");
+    const long long n_work = prep_count_work(n, cout, cin, taps, backward);
+    SLR_CHECK_ARG(n_work >= 0, "sizes (Cout, Cin > 0, taps 9 or 1, fewer than 2^31 work items in all)");
+    const size_t need = prep_total(n, n_work);
+    SLR_CHECK_ARG(bytes >= need, "bytes (slr_conv_prep_plan_bytes at least)");
+    for (int t = 0; t < n; ++t) {
+        SLR_CHECK_ARG(w[t] && wfrag[t] && !((w[t] | wfrag[t]) & 3), "weight and buffer addresses: not null, 4-byte aligned");
+        SLR_CHECK_ARG(slot[t] >= 0, "slot (>= 0)");
+    }
+    char *base = (char *)host_buf;
+    memset(base, 0, need);
+    const unsigned int head32[4] = {SLR_CONV_PREP_PLAN_MAGIC, (unsigned)PREP_CHUNK, (unsigned)n, (unsigned)n_work};
+    const unsigned long long head64[3] = {PREP_HEADER, prep_work_off(n), need};
+    memcpy(base, head32, sizeof head32);
+    memcpy(base + 16, head64, sizeof head64);
+    PrepTensor *tens = (PrepTensor *)(base + PREP_HEADER);
+    PrepWork *work = (PrepWork *)(base + prep_work_off(n));
+    long long k = 0;
+    for (int t = 0; t < n; ++t) {
+        const int co = backward[t] ? cin[t] : cout[t], ci = backward[t] ? cout[t] : cin[t];
+        const int total = (int)prep_elements(cout[t], cin[t], taps[t], backward[t]);
+        tens[t] = {(const float *)w[t], (float *)wfrag[t], slot[t], co, ci, conv_cin_pad(ci), taps[t], backward[t] ? 1 : 0,
+                   taps[t] == 9 && co <= CF_MAXCO ? 1 : 0, total};
+        for (int s = 0; s < total; s += PREP_CHUNK) work[k++] = {t, s};
+    }
+    return 0;
+}
+
+SLR_EXPORT int slr_conv_prep_scaled_multi(const void *plan_dev, int n_tensors, int n_work, const float *scales, void *stream) {
+    SLR_CHECK_ARG(plan_dev && scales, "null pointer (plan or scales)");
+    SLR_CHECK_ARG(n_tensors > 0 && n_work > 0, "n_tensors, n_work (what slr_conv_prep_plan_fill wrote into the plan's header)");
+    SLR_CHECK_ARG(!((uintptr_t)plan_dev & 15) && !((uintptr_t)scales & 3), "plan 16-byte and scales 4-byte aligned");
+    const char *base = (const char *)plan_dev;
+    hipLaunchKernelGGL(conv_weights_plan_kernel, dim3(n_work < PREP_MAX_GRID ? n_work : PREP_MAX_GRID), dim3(256), 0, (hipStream_t)stream,
+                       (const PrepTensor *)(base + PREP_HEADER), (const PrepWork *)(base + prep_work_off(n_tensors)), n_work, scales);
     SLR_CHECK_LAUNCH();
     return 0;
 }

@@ -26,13 +26,28 @@ constexpr int CF_ITEMS = (CF_NPX + CF_THREADS - 1) / CF_THREADS;   // staging it
 
 __host__ __device__ inline int conv_few_cin_pad(int Cin) { return (Cin + 7) / 8 * 8; }
 
-// w [Cout,Cin,3,3] fp32 -> [ci padded to 8][tap][4] fp32, zeros for the padding
-__global__ __launch_bounds__(256) void conv_few_weights_kernel(const float *__restrict__ w, float *__restrict__ wf, int Cout, int Cin, int CinP) {
+// The value a prepared buffer holds for (output channel co, input channel ci, tap) of the convolution it serves, [Cout,Cin,taps]:
+// w[co][ci][tap], or with `backward` the flipped, transposed weight of the backward-data convolution read straight from the forward's
+// w [Cin,Cout,taps] (w.flip(2, 3).transpose(0, 1)[co][ci][tap] = w[ci][co][taps - 1 - tap]); times scale[0] where there is a scale (a
+// device scalar: the 1 / sigma of spectral normalisation), one fp32 product.
+__device__ __forceinline__ float conv_weight_source(const float *__restrict__ w, const float *__restrict__ scale, int co, int ci, int tap,
+                                                    int Cout, int Cin, int taps, int backward) {
+    float x = backward ? w[((size_t)ci * Cout + co) * taps + (taps - 1 - tap)] : w[((size_t)co * Cin + ci) * taps + tap];
+    if (scale) x *= scale[0];
+    return x;
+}
+
+// w [Cout,Cin,3,3] fp32 -> [ci padded to 8][tap][4] fp32, zeros for the padding: element i of the buffer
+__device__ __forceinline__ void conv_few_weights_item(int i, const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ wf,
+                                                      int Cout, int Cin, int backward) {
+    const int co = i & 3, tap = (i >> 2) % 9, ci = i / 36;
+    wf[i] = (co < Cout && ci < Cin) ? conv_weight_source(w, scale, co, ci, tap, Cout, Cin, 9, backward) : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void conv_few_weights_kernel(const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ wf,
+                                                               int Cout, int Cin, int CinP, int backward) {
     const int total = CinP * 36;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int co = i & 3, tap = (i >> 2) % 9, ci = i / 36;
-        wf[i] = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * 9 + tap] : 0.0f;
-    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) conv_few_weights_item(i, w, scale, wf, Cout, Cin, backward);
 }
 
 // NCO: output channels computed (>= Cout)

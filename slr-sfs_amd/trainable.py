@@ -17,13 +17,18 @@ Then the generator's networks (csrc/decoder_grad.hip): the decoder'
 ``TrainablePconvInputBlock`` -- the plain ``TrainableResBlock`` (ResNet_Block, blocks.py:47-87) and the nets made of the two:
 ``TrainableDecoderPconv2``, ``TrainableEncoderWithZ``, ``TrainableEncoder``, ``TrainableBGDecoder``.
 
-Not here: spectral normalisation (the reference trains with --norm_G batch), and BN + ReLU fused into the backward convolution's prologue.
+Spectral normalisation as the reference trains with it (--norm_G sync:spectral_batch; DESIGN 3.14, spectral.py, csrc/spectral.hip): the
+operators take ``weight_scale`` (the 1 / sigma of this forward, a device scalar folded into the weight preparation) and ``spectral`` (the
+saved u and v: the weight gradient is then the one to ``weight_orig``); the layers, blocks and networks take ``spectral=True``.
+
+Not here: BN + ReLU fused into the backward convolution's prologue.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import nets
+from . import spectral as _spectral
 from ._lib import call, lib, require_device
 
 GRAD_X_B8, GRAD_G_B8 = 1, 2              # include/slr_splat.h: SLR_GRAD_X_B8 / SLR_GRAD_G_B8
@@ -100,6 +105,26 @@ def _backward_weights(weight, owner):
     return _forward_weights(bconv.weight, bconv)
 
 
+def _normalised(name, weight, weight_scale, spectral, sn):
+    """The operators' ``weight_scale`` / ``spectral`` arguments, checked, as one ``spectral.Normalised`` (None: no normalisation); ``sn``:
+    the one a ``SpectralGroup`` handed to the layer."""
+    if sn is not None:
+        return sn
+    _spectral.check_spectral(name, weight, weight_scale, spectral)
+    if weight_scale is None:
+        return None
+    u, v = spectral if spectral is not None else (None, None)
+    return _spectral.Normalised(weight_scale.detach(), None if u is None else u.detach(), None if v is None else v.detach())
+
+
+def _weights_of(weight, owner, sn, backward=False):
+    """(buffer, rung flag) of the forward or the backward-data convolution: today's cached preparation, or with a normalisation the
+    buffer of ``weight * scale`` (always the fp32 rung)."""
+    if sn is None:
+        return _backward_weights(weight, owner) if backward else _forward_weights(weight, owner)
+    return sn.buffer(weight, backward), nets.CONV_F32
+
+
 def _conv(x, buf, arith, bias, cout, layout, residual=None):
     N, cin, H, W = x.shape
     out = x.new_empty(N, cout, H, W)
@@ -135,12 +160,13 @@ def _scale_bias(g, r, um, want_gr, want_bias, layout=0):
 
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, in_b8, out_b8, owner, residual=None):
-        buf, arith = _forward_weights(weight, owner)
+    def forward(ctx, x, weight, bias, in_b8, out_b8, owner, residual=None, sn=None):
+        buf, arith = _weights_of(weight, owner, sn)
         layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0) | (nets.RES_B8 if out_b8 and residual is not None else 0)
         out = _conv(x, buf, arith, bias, weight.shape[0], layout, residual)
         ctx.save_for_backward(x, weight)
         ctx.cfg = (in_b8, out_b8, owner, bias is not None)
+        ctx.sn = sn
         return out
 
     @staticmethod
@@ -153,24 +179,32 @@ class _Conv3x3(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
         gx = gw = gb = None
         if need_x:
-            buf, arith = _backward_weights(weight, owner)
+            buf, arith = _weights_of(weight, owner, ctx.sn, True)
             gx = _conv(g, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
         glayout = GRAD_G_B8 if out_b8 else 0
         if need_w:
             gw, gb = _weight_grad(x, g, cout, need_b, (GRAD_X_B8 if in_b8 else 0) | glayout)
+            if ctx.sn is not None:
+                gw = ctx.sn.weight_grad(gw, weight)
         elif need_b:
             _, gb = _scale_bias(g, None, None, False, True, glayout)
-        return gx, gw, gb, None, None, None, (g if ctx.needs_input_grad[6] else None)    # (out = ... + residual)
+        return gx, gw, gb, None, None, None, (g if ctx.needs_input_grad[6] else None), None    # (out = ... + residual)
 
 
-def conv3x3(x, weight, bias=None, *, in_b8=False, out_b8=False, residual=None, _owner=None):
+def conv3x3(x, weight, bias=None, *, in_b8=False, out_b8=False, residual=None, weight_scale=None, spectral=None, _owner=None, _sn=None):
     """conv2d(x, weight, bias, stride 1, padding 1) for a 3x3 ``weight`` [Cout,Cin,3,3], differentiable in x, weight and bias.
 
     in_b8 / out_b8: x / the result (and with them their gradients) are channel-blocked, [N,C/8,H,W,8] in memory under the logical shape
     [N,C,H,W] -- the package's activation layout (nets._b8); C % 8 == 0 then.  ``residual`` [N,Cout,H,W] (in the result's layout) is
-    added in the kernel's epilogue (the x_a + x_b of ResNet_Block, blocks.py:87) and receives the result's gradient."""
+    added in the kernel's epilogue (the x_a + x_b of ResNet_Block, blocks.py:87) and receives the result's gradient.
+
+    weight_scale: a one-element device tensor; the convolution runs with ``weight * weight_scale`` (the factor is folded into the weight
+    preparation: no pass of its own) and the weight gradient is the one to ``weight``, the factor a constant.  spectral=(u, v), with
+    ``weight_scale`` = 1 / sigma of the same forward: ``weight`` is the ``weight_orig`` of torch's spectral_norm and its gradient is
+    ``spectral_weight_grad``'s, (dW - <dW, W_eff> u v^T) / sigma.  Both None: exactly the operator without them."""
     _check("conv3x3", x, weight, bias, in_b8=in_b8, out_b8=out_b8, residual=residual)
-    return _Conv3x3.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, residual)
+    sn = _normalised("conv3x3", weight, weight_scale, spectral, _sn)
+    return _Conv3x3.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, residual, sn)
 
 
 def partial_conv_factors(mask, cin):
@@ -185,10 +219,11 @@ def partial_conv_factors(mask, cin):
 
 class _PartialConv3x3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xm, mask, weight, bias, owner, residual=None, in_b8=False, out_b8=False):
+    def forward(ctx, xm, mask, weight, bias, owner, residual=None, in_b8=False, out_b8=False, sn=None):
         N, cin, H, W = xm.shape
         cout = weight.shape[0]
-        buf, arith = _forward_weights(weight, owner)
+        buf, arith = _weights_of(weight, owner, sn)
+        ctx.sn = sn
         out, um = xm.new_empty(N, cout, H, W), xm.new_empty(N, 1, H, W)
         layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0) | (nets.RES_B8 if out_b8 and residual is not None else 0)
         call("slr_pconv3x3_forward", xm.device, xm, None, None, mask, buf, 1.0, 1.0, bias, residual, None, None, out, um,
@@ -212,47 +247,69 @@ class _PartialConv3x3(torch.autograd.Function):
             r, um = partial_conv_factors(mask, cin)
             gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
             if need_x:
-                buf, arith = _backward_weights(weight, owner)
+                buf, arith = _weights_of(weight, owner, ctx.sn, True)
                 gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
             if need_w:
                 gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
-        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None    # (out = ... + residual)
+                if ctx.sn is not None:
+                    gw = ctx.sn.weight_grad(gw, weight)
+        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None, None    # (out = ... + residual)
 
 
-def partial_conv3x3(xm, mask, weight, bias, *, residual=None, in_b8=False, out_b8=False, _owner=None):
+def partial_conv3x3(xm, mask, weight, bias, *, residual=None, in_b8=False, out_b8=False, weight_scale=None, spectral=None, _owner=None,
+                    _sn=None):
     """``nets.PartialConv.forward(xm, mask, pre_bn=None)``: PartialConv2d(multi_channel=True, return_mask=True) (partialconv2d.py:41-81)
     of the already activated and masked ``xm`` [N,Cin,H,W] with the channel-uniform ``mask`` [N,1,H,W]; returns (out, update_mask).
     Differentiable in xm, weight and bias; mask and update_mask carry no gradient.  ``residual`` [N,Cout,H,W] (in the result's layout) is
-    added in the kernel's epilogue (blocks.py:248) and receives the result's gradient.  in_b8 / out_b8 as ``conv3x3``."""
+    added in the kernel's epilogue (blocks.py:248) and receives the result's gradient.  in_b8 / out_b8, weight_scale / spectral as
+    ``conv3x3``."""
     if bias is None:
         raise ValueError("partial_conv3x3: a bias is required (PartialConv2d adds it inside the mask ratio)")
     _check("partial_conv3x3", xm, weight, bias, mask=mask, in_b8=in_b8, out_b8=out_b8, residual=residual)
-    return _PartialConv3x3.apply(xm, mask.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8))
+    sn = _normalised("partial_conv3x3", weight, weight_scale, spectral, _sn)
+    return _PartialConv3x3.apply(xm, mask.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8), sn)
+
+
+def _learn(conv, spectral):
+    """The parameters of a ``nets.Conv`` learn; spectral=True: as torch's spectral_norm leaves the layer -- the parameter ``weight_orig``,
+    the buffers ``weight_u`` / ``weight_v`` (normalised randn), no ``weight``."""
+    conv.spectral = bool(spectral)
+    conv.weight.requires_grad_(True)
+    if conv.bias is not None:
+        conv.bias.requires_grad_(True)
+    if spectral:
+        _spectral.make_spectral(conv)
+
+
+def _w(conv):
+    return conv.weight_orig if conv.spectral else conv.weight
 
 
 class TrainableConv3x3(nets.Conv):
     """``nets.Conv(cin, cout, 3)`` whose parameters learn: same state-dict keys (``weight``, ``bias``), so what
     ``nets.load_reference_state_dict`` reads for a ``nets.Conv`` drops in."""
 
-    def __init__(self, cin, cout, bias=True):
+    def __init__(self, cin, cout, bias=True, spectral=False):
         super().__init__(cin, cout, 3, bias)
-        self.weight.requires_grad_(True)
-        if self.bias is not None:
-            self.bias.requires_grad_(True)
+        _learn(self, spectral)
 
     def forward(self, x, in_b8=False, out_b8=False, residual=None):
+        if self.spectral:
+            return conv3x3(x, self.weight_orig, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self, _sn=_spectral.take(self))
         return conv3x3(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self)
 
 
 class TrainablePartialConv3x3(nets.PartialConv):
     """``nets.PartialConv(cin, cout, 3)`` whose parameters learn; forward(xm, mask) -> (out, update_mask) as ``partial_conv3x3``."""
 
-    def __init__(self, cin, cout):
+    def __init__(self, cin, cout, spectral=False):
         super().__init__(cin, cout, 3, True)
-        self.weight.requires_grad_(True)
-        self.bias.requires_grad_(True)
+        _learn(self, spectral)
 
     def forward(self, xm, mask, residual=None, in_b8=False, out_b8=False):
+        if self.spectral:
+            return partial_conv3x3(xm, mask, self.weight_orig, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self,
+                                   _sn=_spectral.take(self))
         return partial_conv3x3(xm, mask, self.weight, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self)
 
 
@@ -371,11 +428,12 @@ def bn_relu_mask_train(x, mask, gain, bias, *, mean=None, var=None, eps=1e-5, b8
 
 class _Conv1x1(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, in_b8, out_b8, owner):
-        buf, arith = _forward_weights(weight, owner)
+    def forward(ctx, x, weight, bias, in_b8, out_b8, owner, sn=None):
+        buf, arith = _weights_of(weight, owner, sn)
         out = _conv1(x, buf, arith, bias, weight.shape[0], (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0))
         ctx.save_for_backward(x, weight)
         ctx.cfg = (in_b8, out_b8, owner, bias is not None)
+        ctx.sn = sn
         return out
 
     @staticmethod
@@ -389,16 +447,18 @@ class _Conv1x1(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
         gx = gw = gb = None
         if need_x:                                       # the forward kernel with the transposed weight
-            buf, arith = _backward_weights(weight, owner)
+            buf, arith = _weights_of(weight, owner, ctx.sn, True)
             gx = _conv1(g, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
         glayout = GRAD_G_B8 if out_b8 else 0
         if need_w:
             gw = x.new_empty(cout, cin, 1, 1)
             ws = torch.empty(int(lib().slr_conv1x1_grad_ws_bytes(N, cin, cout, H, W, 0)), dtype=torch.uint8, device=x.device)
             call("slr_conv1x1_weight_grad", x.device, x, g, gw, N, cin, cout, H, W, 0, (GRAD_X_B8 if in_b8 else 0) | glayout, ws, ws.numel())
+            if ctx.sn is not None:
+                gw = ctx.sn.weight_grad(gw, weight)
         if need_b:
             _, gb = _scale_bias(g, None, None, False, True, glayout)
-        return gx, gw, gb, None, None, None
+        return gx, gw, gb, None, None, None, None
 
 
 def _conv1(x, buf, arith, bias, cout, layout):
@@ -408,11 +468,12 @@ def _conv1(x, buf, arith, bias, cout, layout):
     return out
 
 
-def conv1x1(x, weight, bias=None, *, in_b8=False, out_b8=False, _owner=None):
+def conv1x1(x, weight, bias=None, *, in_b8=False, out_b8=False, weight_scale=None, spectral=None, _owner=None, _sn=None):
     """conv2d(x, weight, bias) for a 1x1 ``weight`` [Cout,Cin,1,1] (the block's skip branch, blocks.py:192-193, 243-247) on the fp32 rung,
-    differentiable in x, weight and bias; in_b8 / out_b8 as ``conv3x3``."""
+    differentiable in x, weight and bias; in_b8 / out_b8, weight_scale / spectral as ``conv3x3``."""
     _check("conv1x1", x, weight, bias, in_b8=in_b8, out_b8=out_b8, k=1)
-    return _Conv1x1.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner)
+    sn = _normalised("conv1x1", weight, weight_scale, spectral, _sn)
+    return _Conv1x1.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, sn)
 
 
 class _Resample(torch.autograd.Function):
@@ -449,13 +510,13 @@ def upsample_up(x, b8=False):
 class TrainableConv1x1(nets.Conv):
     """``nets.Conv(cin, cout, 1)`` whose parameters learn (the block's ``conv_b``)."""
 
-    def __init__(self, cin, cout, bias=False):
+    def __init__(self, cin, cout, bias=False, spectral=False):
         super().__init__(cin, cout, 1, bias)
-        self.weight.requires_grad_(True)
-        if self.bias is not None:
-            self.bias.requires_grad_(True)
+        _learn(self, spectral)
 
     def forward(self, x, in_b8=False, out_b8=False):
+        if self.spectral:
+            return conv1x1(x, self.weight_orig, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=_spectral.take(self))
         return conv1x1(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self)
 
 
@@ -464,12 +525,16 @@ class TrainableNoiseBN(nn.Module):
     ``stored_var`` plus the two bias-free linear maps ``gain`` and ``bias`` from the noise [N,noise_sz] (torch ops: [N,20] x [20,C] is
     not tensor-sized).  Training: batch statistics, the stored ones updated with momentum 0.1; eval: stored statistics, zero noise."""
 
-    def __init__(self, ch, noise_sz=20, eps=1e-5, momentum=0.1):
+    def __init__(self, ch, noise_sz=20, eps=1e-5, momentum=0.1, spectral=False):
         super().__init__()
-        self.eps, self.momentum, self.noise_sz = eps, momentum, noise_sz
+        self.eps, self.momentum, self.noise_sz, self.spectral = eps, momentum, noise_sz, bool(spectral)
         self.register_buffer("stored_mean", torch.zeros(ch))
         self.register_buffer("stored_var", torch.ones(ch))
-        self.gain, self.bias = nn.Linear(noise_sz, ch, bias=False), nn.Linear(noise_sz, ch, bias=False)
+        if spectral:                                     # keys gain.weight_orig / gain.weight_u / gain.weight_v, as the reference's
+            self.register_buffer("accumulation_counter", torch.zeros(1))      # normalization.py:167, 266: in its state dicts; carried
+            self.gain, self.bias = _spectral.SpectralLinear(noise_sz, ch), _spectral.SpectralLinear(noise_sz, ch)
+        else:
+            self.gain, self.bias = nn.Linear(noise_sz, ch, bias=False), nn.Linear(noise_sz, ch, bias=False)
 
     def forward(self, x, mask, noise=None, b8=False, fork=False, nonzero=False):
         """relu(bn(x)) * mask (``mask`` None: no mask, the plain BN of the encoder blocks).  ``noise`` [N,noise_sz]; None draws
@@ -477,6 +542,8 @@ class TrainableNoiseBN(nn.Module):
         nonzero=True (``mask`` None): the per-element mask x != 0 of the decoder's first block, ``bn_relu_nonzero_train``'s tuple."""
         if nonzero and mask is not None:
             raise ValueError("TrainableNoiseBN: nonzero=True derives the mask from x; pass mask=None")
+        if self.spectral:
+            _spectral.begin(self)
         if noise is None:
             noise = (torch.randn if self.training else torch.zeros)(x.shape[0], self.noise_sz, device=x.device, dtype=x.dtype)
         gain, bias = (1.0 + self.gain(noise)).contiguous(), self.bias(noise).contiguous()
@@ -495,11 +562,14 @@ class TrainablePconvResBlock(nets.PconvResBlock):
     eval mode: same sub-module names and state-dict keys (``nets.load_reference_state_dict`` fills it), the BNs with their noise weights
     ``bn1.gain.weight`` ... as extra keys."""
 
-    def __init__(self, cin, cout, resample=None):
+    def __init__(self, cin, cout, resample=None, spectral=False):
         super().__init__(cin, cout, resample)
-        self.bn1, self.bn2 = TrainableNoiseBN(cin), TrainableNoiseBN(cout)
-        self.conv_aa, self.conv_ab = TrainablePartialConv3x3(cin, cout), TrainablePartialConv3x3(cout, cout)
-        self.conv_b = TrainableConv1x1(cin, cout) if self.conv_b is not None else None
+        self.spectral = sn = bool(spectral)
+        self.bn1, self.bn2 = TrainableNoiseBN(cin, spectral=sn), TrainableNoiseBN(cout, spectral=sn)
+        self.conv_aa, self.conv_ab = TrainablePartialConv3x3(cin, cout, spectral=sn), TrainablePartialConv3x3(cout, cout, spectral=sn)
+        self.conv_b = TrainableConv1x1(cin, cout, spectral=sn) if self.conv_b is not None else None
+        if sn and self.conv_b is None:                   # the reference builds conv_b in every block (blocks.py:192-195): keep its tensors
+            self.conv_b_unused = _spectral.UnusedSpectralConv(cin, cout)
         self.kind = resample
 
     def forward(self, x, mask, b8_in=False, noise=None):
@@ -509,7 +579,9 @@ class TrainablePconvResBlock(nets.PconvResBlock):
         if mask is None:
             raise ValueError("TrainablePconvResBlock: an explicit mask [N,1,H,W] is required (the per-element mask x != 0 is TrainablePconvInputBlock's)")
         _check_planes("TrainablePconvResBlock", x, b8_in, mask)
-        cout = self.conv_aa.weight.shape[0]
+        if self.spectral:
+            _spectral.begin(self)
+        cout = _w(self.conv_aa).shape[0]
         b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
         n1, n2 = noise if noise is not None else (None, None)
         a, _, _, xs = self.bn1(x, mask, n1, b8=b8_in, fork=True)                    # blocks.py:225-231
@@ -620,10 +692,11 @@ def partial_conv_factors_counts(msum, cin):
 
 class _PartialConv3x3Counts(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xm, msum, weight, bias, owner, residual=None, in_b8=False, out_b8=False):
+    def forward(ctx, xm, msum, weight, bias, owner, residual=None, in_b8=False, out_b8=False, sn=None):
         N, cin, H, W = xm.shape
         cout = weight.shape[0]
-        buf, arith = _forward_weights(weight, owner)
+        buf, arith = _weights_of(weight, owner, sn)
+        ctx.sn = sn
         ratio, um = _factors_counts(msum, cin)
         out = _conv(xm, buf, arith, None, cout, (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0))
         call("slr_pconv_train_epilogue", xm.device, out, ratio, um, bias, residual, out, N, cout, H, W, int(out_b8))
@@ -645,22 +718,26 @@ class _PartialConv3x3Counts(torch.autograd.Function):
         if need_x or need_w or need_b:                   # from here on exactly _PartialConv3x3.backward
             gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
             if need_x:
-                buf, arith = _backward_weights(weight, owner)
+                buf, arith = _weights_of(weight, owner, ctx.sn, True)
                 gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
             if need_w:
                 gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
-        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None
+                if ctx.sn is not None:
+                    gw = ctx.sn.weight_grad(gw, weight)
+        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None, None
 
 
-def partial_conv3x3_counts(xm, msum, weight, bias, *, residual=None, in_b8=False, out_b8=False, _owner=None):
+def partial_conv3x3_counts(xm, msum, weight, bias, *, residual=None, in_b8=False, out_b8=False, weight_scale=None, spectral=None,
+                           _owner=None, _sn=None):
     """``partial_conv3x3`` for a per-element mask given as its count plane: ``xm`` [N,Cin,H,W] already activated and masked, ``msum``
     [N,1,H,W] = sum_c mask (``bn_relu_nonzero_train``'s).  A bias-free convolution on the fp32 rung, then
     out = (raw * ratio + bias) * um (+ residual) with the factors of ``partial_conv_factors_counts``; returns (out, update_mask).
-    Differentiable in xm, weight, bias and residual."""
+    Differentiable in xm, weight, bias and residual; weight_scale / spectral as ``conv3x3``."""
     if bias is None:
         raise ValueError("partial_conv3x3_counts: a bias is required (PartialConv2d adds it inside the mask ratio)")
     _check("partial_conv3x3_counts", xm, weight, bias, mask=msum, in_b8=in_b8, out_b8=out_b8, residual=residual)
-    return _PartialConv3x3Counts.apply(xm, msum.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8))
+    sn = _normalised("partial_conv3x3_counts", weight, weight_scale, spectral, _sn)
+    return _PartialConv3x3Counts.apply(xm, msum.detach(), weight, bias, _owner, residual, bool(in_b8), bool(out_b8), sn)
 
 
 class TrainablePconvInputBlock(TrainablePconvResBlock):
@@ -670,11 +747,14 @@ class TrainablePconvInputBlock(TrainablePconvResBlock):
     def forward(self, x, b8_in=False, noise=None):
         """-> (y, update_mask, b8_out); arguments as the parent's, without the mask."""
         _check_planes("TrainablePconvInputBlock", x, b8_in)
-        cout = self.conv_aa.weight.shape[0]
+        if self.spectral:
+            _spectral.begin(self)
+        cout = _w(self.conv_aa).shape[0]
         b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
         n1, n2 = noise if noise is not None else (None, None)
         a, _, _, msum, xs = self.bn1(x, None, n1, b8=b8_in, fork=True, nonzero=True)             # blocks.py:225-231
-        a, m = partial_conv3x3_counts(a, msum, self.conv_aa.weight, self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa)
+        a, m = partial_conv3x3_counts(a, msum, _w(self.conv_aa), self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa,
+                                      _sn=_spectral.take(self.conv_aa) if self.spectral else None)
         a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238 -- the mask is channel-uniform from here
         skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs
         a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)
@@ -692,17 +772,20 @@ class TrainableResBlock(nets.ResBlock):
     batch-norm without a mask (manual_bn), two 3x3 convolutions, the 1x1 skip convolution with its bias.  Same sub-module names and
     state-dict keys, the BNs' noise layers as extra keys."""
 
-    def __init__(self, cin, cout, resample=None):
+    def __init__(self, cin, cout, resample=None, spectral=False):
         super().__init__(cin, cout, resample)
-        self.bn1, self.bn2 = TrainableNoiseBN(cin), TrainableNoiseBN(cout)
-        self.conv_aa, self.conv_ab = TrainableConv3x3(cin, cout), TrainableConv3x3(cout, cout)
-        self.conv_b = TrainableConv1x1(cin, cout, bias=True) if self.conv_b is not None else None
+        self.spectral = sn = bool(spectral)
+        self.bn1, self.bn2 = TrainableNoiseBN(cin, spectral=sn), TrainableNoiseBN(cout, spectral=sn)
+        self.conv_aa, self.conv_ab = TrainableConv3x3(cin, cout, spectral=sn), TrainableConv3x3(cout, cout, spectral=sn)
+        self.conv_b = TrainableConv1x1(cin, cout, bias=True, spectral=sn) if self.conv_b is not None else None
         self.kind = resample
 
     def forward(self, x, b8_in=False, noise=None):
         """-> (y, b8_out).  bn1 -> conv_aa -> bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue -> one resampling of the sum."""
         _check_planes("TrainableResBlock", x, b8_in)
-        cout = self.conv_aa.weight.shape[0]
+        if self.spectral:
+            _spectral.begin(self)
+        cout = _w(self.conv_aa).shape[0]
         b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
         n1, n2 = noise if noise is not None else (None, None)
         a, _, _, xs = self.bn1(x, None, n1, b8=b8_in, fork=True)                    # blocks.py:69-72
@@ -743,6 +826,8 @@ class _TrainableResNet:
     """forward of the nets made of ``TrainableResBlock``s: the blocks in order, NCHW at the end."""
 
     def _run(self, x, noise):
+        if self.spectral:                                # sigma of every tensor and every prepared buffer: at most four launches for the network
+            _spectral.begin(self, force=True)
         b8 = False
         for blk, nz in zip(self.blocks, _noise_of(noise, len(self.blocks))):
             x, b8 = blk(x, b8, noise=nz)
@@ -754,11 +839,12 @@ class TrainableEncoderWithZ(_TrainableResNet, nets.EncoderWithZ):
     """``nets.EncoderWithZ`` (ResNetEncoder_with_Z, architectures.py:155-197) whose weights learn.  widths: the seven inner widths
     (default nets._ENC[1:]); updown: the eight blocks' resampling (default none)."""
 
-    def __init__(self, cin=3, feat=64, *, widths=None, updown=None):
+    def __init__(self, cin=3, feat=64, *, widths=None, updown=None, spectral=False):
         nn.Module.__init__(self)
+        self.spectral = bool(spectral)
         n = len(nets._ENC[1:] if widths is None else widths) + 1
         ch, ud = _net_plan("TrainableEncoderWithZ", cin, nets._ENC[1:], feat + 1, widths, updown, [None] * n)
-        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i], spectral) for i in range(len(ud)))
 
     def forward(self, x, noise=None):
         x = self._run(x, noise)
@@ -768,11 +854,12 @@ class TrainableEncoderWithZ(_TrainableResNet, nets.EncoderWithZ):
 class TrainableEncoder(_TrainableResNet, nets.Encoder):
     """``nets.Encoder`` (ResNetEncoder, architectures.py:121-153) whose weights learn; widths / updown as ``TrainableEncoderWithZ``."""
 
-    def __init__(self, cin=3, cout=2, *, widths=None, updown=None):
+    def __init__(self, cin=3, cout=2, *, widths=None, updown=None, spectral=False):
         nn.Module.__init__(self)
+        self.spectral = bool(spectral)
         n = len(nets._ENC[1:] if widths is None else widths) + 1
         ch, ud = _net_plan("TrainableEncoder", cin, nets._ENC[1:], cout, widths, updown, [None] * n)
-        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i], spectral) for i in range(len(ud)))
 
     def forward(self, x, noise=None):
         return self._run(x, noise)
@@ -782,10 +869,11 @@ class TrainableBGDecoder(_TrainableResNet, nets.BGDecoder):
     """``nets.BGDecoder`` (ResNetBGDecoder, architectures.py:233-260) whose weights learn.  widths: the inner widths (default nets._DEC);
     updown: the blocks' resampling (default nets._UPDOWN)."""
 
-    def __init__(self, cin=3, cout=3, *, widths=None, updown=None):
+    def __init__(self, cin=3, cout=3, *, widths=None, updown=None, spectral=False):
         nn.Module.__init__(self)
+        self.spectral = bool(spectral)
         ch, ud = _net_plan("TrainableBGDecoder", cin, nets._DEC, cout, widths, updown, nets._UPDOWN)
-        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+        self.blocks = nn.ModuleList(TrainableResBlock(ch[i], ch[i + 1], ud[i], spectral) for i in range(len(ud)))
 
     def forward(self, x, noise=None):
         return self._run(x, noise)
@@ -795,12 +883,16 @@ class TrainableDecoderPconv2(nets.DecoderPconv2):
     """``nets.DecoderPconv2`` (ResNetDecoderPconv2, architectures.py:345-375) whose weights learn: block 0 is a
     ``TrainablePconvInputBlock`` (mask = x != 0, :369), the others ``TrainablePconvResBlock``s.  widths / updown as ``TrainableBGDecoder``."""
 
-    def __init__(self, cin=64, cout=3, *, widths=None, updown=None):
+    def __init__(self, cin=64, cout=3, *, widths=None, updown=None, spectral=False):
         nn.Module.__init__(self)
+        self.spectral = bool(spectral)
         ch, ud = _net_plan("TrainableDecoderPconv2", cin, nets._DEC, cout, widths, updown, nets._UPDOWN)
-        self.blocks = nn.ModuleList((TrainablePconvResBlock if i else TrainablePconvInputBlock)(ch[i], ch[i + 1], ud[i]) for i in range(len(ud)))
+        self.blocks = nn.ModuleList((TrainablePconvResBlock if i else TrainablePconvInputBlock)(ch[i], ch[i + 1], ud[i], spectral)
+                                    for i in range(len(ud)))
 
     def forward(self, x, noise=None):
+        if self.spectral:
+            _spectral.begin(self, force=True)
         noise = _noise_of(noise, len(self.blocks))
         x, mask, b8 = self.blocks[0](x, False, noise=noise[0])
         for blk, nz in zip(self.blocks[1:], noise[1:]):
