@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 20
+#define SLR_ABI_VERSION 21
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -919,6 +919,44 @@ size_t slr_spectral_grad_ws_bytes(int rows, int cols);
  * out may be dw.  ws: 16-byte aligned, slr_spectral_grad_ws_bytes bytes, else SLR_E_WORKSPACE. */
 int slr_spectral_weight_grad(const float *dw, const float *w, const float *u, const float *v, const float *inv_sigma, float *out,
                              int rows, int cols, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ the same gradient for every tensor of a list (ABI 21; csrc/spectral.hip)
+ * slr_spectral_weight_grad over ANY number of tensors in TWO launches: what a network's backward needs once for all its weight_orig,
+ * instead of two launch-bound launches per tensor.  Built like slr_adam_step and slr_spectral_sigma: a plan in device memory, never
+ * kernel arguments.  Work items are (tensor, chunk) pairs, chunk c of a tensor its elements [c, c + 1) SLR_SPECTRAL_GRAD_CHUNK.
+ *
+ * Plan (little endian; offsets in bytes from the plan's start, which is 16-byte aligned):
+ *   header, 64 bytes:   uint32 magic = SLR_SPECTRAL_GRAD_PLAN_MAGIC, uint32 chunk = SLR_SPECTRAL_GRAD_CHUNK, uint32 n_tensors, uint32 n_work,
+ *                       uint64 tensors_off = 64, uint64 bytes, uint64 work_off, uint64 scratch_off, 16 bytes of zeros
+ *   tensors_off:        n_tensors records of 64 bytes: uint64 dw, w, out (device addresses), int32 rows, int32 cols, int32 slot (its
+ *                       element of inv_sigma), int32 chunks = ceil(rows cols / chunk), int64 u_off, int64 v_off (elements into saved_u /
+ *                       saved_v: where slr_spectral_sigma of that forward put its u and v), int64 first (its first work item: the running
+ *                       sum of chunks; its partial sums are doubles [first, first + chunks) of the scratch)
+ *   work_off:           n_work records of 8 bytes: int32 tensor, int32 chunk -- every tensor's chunks in order, the tensors in order
+ *   scratch_off:        n_work doubles, one per work item, written by every call before it reads them
+ *   work_off = align16(64 + 64 n_tensors), scratch_off = align256(work_off + 8 n_work), bytes = scratch_off + align256(8 n_work).
+ * The scratch belongs to the plan: calls that share a plan run on one stream. */
+#define SLR_SPECTRAL_GRAD_PLAN_MAGIC 0x44475053u   /* "SPGD" */
+
+/* Bytes of the plan of n tensors of rows[t] x cols[t] (host arithmetic only); 0 for n <= 0 or a size outside 1 .. SLR_SPECTRAL_MAX_DIM. */
+size_t slr_spectral_grad_plan_bytes(int n, const int *rows, const int *cols);
+
+/* Writes the plan into CALLER memory `host_buf` of `bytes` >= slr_spectral_grad_plan_bytes(n, rows, cols) bytes (host only; nothing
+ * touches a device).  dw, w, out: n device addresses each, as integers, 4-byte aligned; out[t] may be dw[t].  u_off, v_off, slot: where
+ * tensor t's u, v and inv_sigma lie in the arrays of its forward (the layout slr_spectral_sigma wrote; any subset of that list, in any
+ * order, is a legal list here).  SLR_E_BADARG for n <= 0, a null or misaligned address, a size outside 1 .. SLR_SPECTRAL_MAX_DIM, a
+ * negative offset or slot, or too few bytes. */
+int slr_spectral_grad_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *dw, const unsigned long long *w,
+                                const unsigned long long *out, const int *rows, const int *cols, const long long *u_off,
+                                const long long *v_off, const int *slot);
+
+/* out_t = (dw_t - <dw_t, w_t inv_sigma_t> u_t v_t^T) inv_sigma_t for every tensor of the plan (a copy of a filled plan in device memory;
+ * n_tensors, n_work: the header's).  Launch 1: a workgroup per work item writes its chunk's sum of dw w, in double, into the scratch.
+ * Launch 2: a workgroup per work item adds its own tensor's partials in chunk order and writes its chunk of out.  Per tensor the
+ * chunking, the order of every sum and the arithmetic are slr_spectral_weight_grad's: the result is BIT-EQUAL to it, alone or in any
+ * list.  No atomics, nothing synchronises. */
+int slr_spectral_weight_grad_multi(void *plan_dev, int n_tensors, int n_work, const float *inv_sigma, const float *saved_u,
+                                   const float *saved_v, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,9 @@ from .adversarial import (conv4x4, instnorm_lrelu, spectral_weight, TrainableNLa
                           TrainableMultiscaleDiscriminator, GANLoss, DiscriminatorLoss)
 from .optim import Adam, TrainingOptimizers  # noqa: F401
 from .spectral import SpectralGroup, SpectralLinear, spectral_sigma, prepare_scaled, spectral_weight_grad, load_spectral_state_dict, reference_state_dict  # noqa: F401
+from .spectral import spectral_weight_grad_multi, defer_weight_grad  # noqa: F401
+from . import model  # noqa: F401
+from .model import TrainingModel, Trainer  # noqa: F401
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401
 from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all  # noqa: F401
 from .dropin import install_into_reference  # noqa: F401

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 20
+ABI_VERSION = 21
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
@@ -127,6 +127,9 @@ SIGNATURES = {
     "slr_conv_prep_scaled_multi": (_i, [_vp, _i, _i, _fp, _vp]),
     "slr_spectral_grad_ws_bytes": (_sz, [_i, _i]),
     "slr_spectral_weight_grad": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _vp, _sz, _vp]),
+    "slr_spectral_grad_plan_bytes": (_sz, [_i, _vp, _vp]),
+    "slr_spectral_grad_plan_fill": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slr_spectral_weight_grad_multi": (_i, [_vp, _i, _i, _fp, _fp, _fp, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

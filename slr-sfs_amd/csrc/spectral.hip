@@ -1,4 +1,4 @@
-// spectral.hip -- spectral normalisation of the generator's weights (ABI 20): what torch.nn.utils.spectral_norm does for every 3x3, partial
+// spectral.hip -- spectral normalisation of the generator's weights (ABI 20; the list-wide gradient: ABI 21): what torch.nn.utils.spectral_norm does for every 3x3, partial
 // 3x3 and 1x1 convolution and every noise linear of the reference's generator under --norm_G sync:spectral_batch (models/layers/blocks.py:5-35,
 // models/layers/normalization.py:6-16), over ANY number of weight matrices in one launch.  A plan in device memory (layout:
 // include/slr_splat.h) lists the matrices; it is never passed as kernel arguments.  No atomics, nothing synchronises, every sum is
@@ -20,6 +20,8 @@
 //   (c) spectral_dot_kernel + spectral_grad_kernel: the gradient to weight_orig from the gradient dW at the effective weight
 //       W_eff = weight_orig * inv_sigma:  (dW - <dW, W_eff> u v^T) * inv_sigma, u and v the constants of that forward.  Chunk partials of
 //       <dW, weight_orig> in double, then every workgroup of the update adds the partials in chunk order.
+//   (d) spectral_dot_multi_kernel + spectral_grad_multi_kernel (ABI 21): (c) for every tensor of a list in two launches, whatever the
+//       list -- a workgroup per (tensor, chunk) of a plan in device memory, the chunk bodies of (c): bit-equal to (c) on each tensor.
 #include <math.h>
 #include <string.h>
 
@@ -294,32 +296,28 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_sigma_kernel(const char
     if (tid == 0) inv_sigma[t.slot] = (float)(1.0 / sigma);
 }
 
-// (c) launch 1: partial[k] = sum over chunk k of dW[i] * W[i], in double
-__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_dot_kernel(const float *__restrict__ dw, const float *__restrict__ w, long long numel,
-                                                                         double *__restrict__ partial) {
-    __shared__ double red[1][SPEC_GRAD_THREADS / 64];
-    const long long start = (long long)blockIdx.x * SPEC_CHUNK;
+// (c) the chunk bodies, shared by the single-tensor and the list-wide kernels: one source, one order of every sum, the same bits.
+// Chunk `chunk` of <dW, W>: thread-strided in double, wave butterfly, waves in order; thread 0 holds the sum.
+__device__ __forceinline__ double spec_chunk_dot(const float *dw, const float *w, long long numel, int chunk, double (*red)[SPEC_GRAD_THREADS / 64]) {
+    const long long start = (long long)chunk * SPEC_CHUNK;
     const int count = (int)(numel - start < SPEC_CHUNK ? numel - start : SPEC_CHUNK);
     double s[1] = {0.0};
     for (int i = threadIdx.x; i < count; i += SPEC_GRAD_THREADS) s[0] += (double)dw[start + i] * (double)w[start + i];
     block_sum<1, SPEC_GRAD_THREADS / 64>(s, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
+    return s[0];
 }
 
-// (c) launch 2: out = (dW - d u v^T) * inv_sigma with d = inv_sigma * sum_k partial[k], the partials added in chunk order by every workgroup
-__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_grad_kernel(const float *dw, const float *__restrict__ u,
-                                                                          const float *__restrict__ v, const float *__restrict__ inv_sigma,
-                                                                          const double *__restrict__ partial, int n_chunks, float *out,
-                                                                          long long numel, int cols) {
-    __shared__ double dshared;
+// Chunk `chunk` of out = (dW - d u v^T) * inv_sigma with d = inv_sigma * sum_k partial[k], the partials added in chunk order.  out may be dw.
+__device__ __forceinline__ void spec_chunk_grad(const float *dw, const float *u, const float *v, const float *inv_sigma, const double *partial,
+                                                int n_chunks, float *out, long long numel, int cols, int chunk, double *dshared) {
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int k = 0; k < n_chunks; ++k) s += partial[k];
-        dshared = s;
+        *dshared = s;
     }
     __syncthreads();
-    const double is = (double)inv_sigma[0], d = dshared * is;
-    const long long start = (long long)blockIdx.x * SPEC_CHUNK;
+    const double is = (double)inv_sigma[0], d = *dshared * is;
+    const long long start = (long long)chunk * SPEC_CHUNK;
     const int count = (int)(numel - start < SPEC_CHUNK ? numel - start : SPEC_CHUNK);
     for (int i = threadIdx.x; i < count; i += SPEC_GRAD_THREADS) {
         const long long e = start + i;
@@ -328,10 +326,71 @@ __global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_grad_kernel(const 
     }
 }
 
+// (c) launch 1: partial[k] = sum over chunk k of dW[i] * W[i], in double
+__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_dot_kernel(const float *__restrict__ dw, const float *__restrict__ w, long long numel,
+                                                                         double *__restrict__ partial) {
+    __shared__ double red[1][SPEC_GRAD_THREADS / 64];
+    const double s = spec_chunk_dot(dw, w, numel, (int)blockIdx.x, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// (c) launch 2: out = (dW - d u v^T) * inv_sigma, every workgroup adding the partials in chunk order
+__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_grad_kernel(const float *dw, const float *__restrict__ u,
+                                                                          const float *__restrict__ v, const float *__restrict__ inv_sigma,
+                                                                          const double *__restrict__ partial, int n_chunks, float *out,
+                                                                          long long numel, int cols) {
+    __shared__ double dshared;
+    spec_chunk_grad(dw, u, v, inv_sigma, partial, n_chunks, out, numel, cols, (int)blockIdx.x, &dshared);
+}
+
+// (d) the same for every tensor of a list in two launches, a workgroup per (tensor, chunk) of the plan: the chunk bodies of (c) on the
+// tensor's own chunks, its partials in its own doubles of the plan's scratch -- nothing of one tensor's result depends on the others.
+struct SpecGradTensor {                                // 64 bytes
+    const float *dw, *w;
+    float *out;
+    int rows, cols, slot, chunks;
+    long long u_off, v_off;                            // in elements, into the saved arrays of the forward
+    long long first;                                   // its first work item: its partials are doubles [first, first + chunks) of the scratch
+};
+static_assert(sizeof(SpecGradTensor) == 64, "the documented plan layout");
+
+__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_dot_multi_kernel(const SpecGradTensor *__restrict__ tens, const SpecWork *__restrict__ work,
+                                                                               double *__restrict__ scratch) {
+    __shared__ double red[1][SPEC_GRAD_THREADS / 64];
+    const SpecWork wk = work[blockIdx.x];
+    const SpecGradTensor t = tens[wk.tensor];
+    const double s = spec_chunk_dot(t.dw, t.w, (long long)t.rows * t.cols, wk.band, red);
+    if (threadIdx.x == 0) scratch[t.first + wk.band] = s;
+}
+
+__global__ __launch_bounds__(SPEC_GRAD_THREADS) void spectral_grad_multi_kernel(const SpecGradTensor *__restrict__ tens, const SpecWork *__restrict__ work,
+                                                                                const double *__restrict__ scratch, const float *__restrict__ inv_sigma,
+                                                                                const float *__restrict__ saved_u, const float *__restrict__ saved_v) {
+    __shared__ double dshared;
+    const SpecWork wk = work[blockIdx.x];
+    const SpecGradTensor t = tens[wk.tensor];
+    spec_chunk_grad(t.dw, saved_u + t.u_off, saved_v + t.v_off, inv_sigma + t.slot, scratch + t.first, t.chunks, t.out, (long long)t.rows * t.cols,
+                    t.cols, wk.band, &dshared);
+}
+
 static long long spec_chunks(int rows, int cols) {
     if (rows <= 0 || cols <= 0) return -1;
     const long long numel = (long long)rows * cols;
     return numel < (1LL << 40) ? (numel + SPEC_CHUNK - 1) / SPEC_CHUNK : -1;
+}
+
+inline size_t spec_grad_work_off(int n) { return (SPEC_HEADER + (size_t)n * sizeof(SpecGradTensor) + 15) & ~(size_t)15; }
+inline size_t spec_grad_scratch_off(int n, long long n_work) { return al256(spec_grad_work_off(n) + (size_t)n_work * sizeof(SpecWork)); }
+inline size_t spec_grad_total(int n, long long n_work) { return spec_grad_scratch_off(n, n_work) + al256((size_t)n_work * sizeof(double)); }
+// work items (chunks) of the list, or -1 where it is not a legal one
+static long long spec_grad_count(int n, const int *rows, const int *cols) {
+    if (n <= 0 || !rows || !cols) return -1;
+    long long work = 0;
+    for (int t = 0; t < n; ++t) {
+        if (rows[t] <= 0 || cols[t] <= 0 || rows[t] > SLR_SPECTRAL_MAX_DIM || cols[t] > SLR_SPECTRAL_MAX_DIM) return -1;
+        work += spec_chunks(rows[t], cols[t]);
+    }
+    return work;
 }
 
 }  // namespace slr
@@ -428,6 +487,62 @@ SLR_EXPORT int slr_spectral_weight_grad(const float *dw, const float *w, const f
     SLR_CHECK_LAUNCH();
     hipLaunchKernelGGL(spectral_grad_kernel, dim3((unsigned)chunks), dim3(SPEC_GRAD_THREADS), 0, st, dw, u, v, inv_sigma, (const double *)ws,
                        (int)chunks, out, numel, cols);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+SLR_EXPORT size_t slr_spectral_grad_plan_bytes(int n, const int *rows, const int *cols) {
+    const long long work = spec_grad_count(n, rows, cols);
+    return work < 0 || work >= (1LL << 31) ? 0 : spec_grad_total(n, work);
+}
+
+SLR_EXPORT int slr_spectral_grad_plan_fill(void *host_buf, size_t bytes, int n, const unsigned long long *dw, const unsigned long long *w,
+                                           const unsigned long long *out, const int *rows, const int *cols, const long long *u_off,
+                                           const long long *v_off, const int *slot) {
+    SLR_CHECK_ARG(n > 0, "n (at least one tensor)");
+    SLR_CHECK_ARG(host_buf && dw && w && out && rows && cols && u_off && v_off && slot, "null pointer");
+    const long long n_work = spec_grad_count(n, rows, cols);
+    SLR_CHECK_ARG(n_work >= 0 && n_work < (1LL << 31), "rows, cols (1 .. SLR_SPECTRAL_MAX_DIM)");
+    const size_t need = spec_grad_total(n, n_work);
+    SLR_CHECK_ARG(bytes >= need, "bytes (slr_spectral_grad_plan_bytes(n, rows, cols) at least)");
+    for (int t = 0; t < n; ++t) {
+        SLR_CHECK_ARG(dw[t] && w[t] && out[t], "null tensor pointer");
+        SLR_CHECK_ARG(!((dw[t] | w[t] | out[t]) & 3), "4-byte aligned tensors");
+        SLR_CHECK_ARG(u_off[t] >= 0 && v_off[t] >= 0 && slot[t] >= 0, "u_off, v_off, slot (not negative)");
+    }
+    char *base = (char *)host_buf;
+    memset(base, 0, spec_grad_scratch_off(n, n_work));  // (the scratch behind it is written before it is read: left as it is)
+    SpecGradTensor *tens = (SpecGradTensor *)(base + SPEC_HEADER);
+    SpecWork *work = (SpecWork *)(base + spec_grad_work_off(n));
+    long long k = 0;
+    for (int t = 0; t < n; ++t) {
+        const int chunks = (int)spec_chunks(rows[t], cols[t]);
+        tens[t] = {(const float *)dw[t], (const float *)w[t], (float *)out[t], rows[t], cols[t], slot[t], chunks, u_off[t], v_off[t], k};
+        for (int i = 0; i < chunks; ++i) work[k++] = {t, i};
+    }
+    const unsigned int head32[4] = {SLR_SPECTRAL_GRAD_PLAN_MAGIC, (unsigned)SPEC_CHUNK, (unsigned)n, (unsigned)n_work};
+    const unsigned long long head64[4] = {SPEC_HEADER, need, spec_grad_work_off(n), spec_grad_scratch_off(n, n_work)};
+    memcpy(base, head32, sizeof head32);
+    memcpy(base + 16, head64, sizeof head64);
+    return 0;
+}
+
+SLR_EXPORT int slr_spectral_weight_grad_multi(void *plan_dev, int n_tensors, int n_work, const float *inv_sigma, const float *saved_u,
+                                              const float *saved_v, void *stream) {
+    SLR_CHECK_ARG(plan_dev && inv_sigma && saved_u && saved_v, "null pointer");
+    SLR_CHECK_ARG(n_tensors > 0, "n_tensors (at least one tensor)");
+    SLR_CHECK_ARG(n_work >= n_tensors, "n_work (what slr_spectral_grad_plan_fill wrote into the plan's header)");
+    SLR_CHECK_ARG(!((uintptr_t)plan_dev & 15) && !(((uintptr_t)inv_sigma | (uintptr_t)saved_u | (uintptr_t)saved_v) & 3),
+                  "plan 16-byte, arrays 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)plan_dev;
+    const SpecGradTensor *tens = (const SpecGradTensor *)(base + SPEC_HEADER);
+    const SpecWork *work = (const SpecWork *)(base + spec_grad_work_off(n_tensors));
+    double *scratch = (double *)(base + spec_grad_scratch_off(n_tensors, n_work));
+    hipLaunchKernelGGL(spectral_dot_multi_kernel, dim3((unsigned)n_work), dim3(SPEC_GRAD_THREADS), 0, st, tens, work, scratch);
+    SLR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(spectral_grad_multi_kernel, dim3((unsigned)n_work), dim3(SPEC_GRAD_THREADS), 0, st, tens, work, (const double *)scratch,
+                       inv_sigma, saved_u, saved_v);
     SLR_CHECK_LAUNCH();
     return 0;
 }

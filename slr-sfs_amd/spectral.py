@@ -7,7 +7,10 @@ training mode.
 ``SpectralGroup`` does this for every normalised tensor of a network in at most four launches, whatever their number (csrc/spectral.hip,
 csrc/conv.hip): ``slr_spectral_sigma`` (power iteration, 1 / sigma, the copies of u and v the backward needs) and
 ``slr_conv_prep_scaled_multi`` (the forward and backward fragment buffers of every convolution, scaled by its 1 / sigma).
-``spectral_weight_grad`` is the gradient to ``weight_orig`` (``slr_spectral_weight_grad``).  The loader takes a reference state dict
+``spectral_weight_grad`` is the gradient to ``weight_orig`` (``slr_spectral_weight_grad``, two launches per tensor);
+``spectral_weight_grad_multi`` is the same for a list of tensors in two launches, bit-equal per tensor
+(``slr_spectral_weight_grad_multi``), and ``defer_weight_grad`` makes a network's group use it: one pair per forward's backward instead
+of one per layer.  The loader takes a reference state dict
 without folding, ``reference_state_dict`` writes one.  Nothing synchronises the host.  There is no fallback: CPU tensors raise.
 """
 import ctypes
@@ -21,6 +24,7 @@ from torch import nn
 from ._lib import call, check, lib
 
 EPS = 1e-12                                              # torch.nn.utils.spectral_norm's default
+MAX_DIM = 3072                                           # SLR_SPECTRAL_MAX_DIM of include/slr_splat.h: rows and cols of one matrix
 
 
 def _require(name, t, shape=None, what="tensor"):
@@ -82,14 +86,67 @@ def _weight_grad(dw, weight_orig, u, v, inv_sigma):
     return out
 
 
+def _grad_plan(dws, weights, outs, offsets, slots, device):
+    """The uploaded plan of ``slr_spectral_weight_grad_multi``: (device copy, the pinned host block it came from, n_work)."""
+    n = len(dws)
+    addr = [np.array([t.data_ptr() for t in ts], dtype=np.uint64) for ts in (dws, weights, outs)]
+    rows = np.array([w.shape[0] for w in weights], dtype=np.int32)
+    cols = np.array([w.numel() // w.shape[0] for w in weights], dtype=np.int32)
+    u_off = np.array([o[0] for o in offsets], dtype=np.int64)
+    v_off = np.array([o[1] for o in offsets], dtype=np.int64)
+    slot = np.array(slots, dtype=np.int32)
+    nbytes = int(lib().slr_spectral_grad_plan_bytes(n, rows.ctypes.data, cols.ctypes.data))
+    if nbytes == 0:
+        raise ValueError(f"spectral_weight_grad_multi: a matrix side outside 1 .. {MAX_DIM} (or an empty list)")
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)              # a fresh pinned block per plan: an earlier upload may be in flight
+    check(lib().slr_spectral_grad_plan_fill(host.data_ptr(), nbytes, n, *(a.ctypes.data for a in addr), rows.ctypes.data, cols.ctypes.data,
+                                            u_off.ctypes.data, v_off.ctypes.data, slot.ctypes.data), "slr_spectral_grad_plan_fill")
+    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    dev.copy_(host, non_blocking=True)
+    return dev, host, int(host.numpy()[12:16].view(np.uint32)[0])
+
+
+def spectral_weight_grad_multi(dws, weights, saved_u, saved_v, offsets, inv_sigma, slots=None, inplace=False):
+    """``spectral_weight_grad`` of every tensor of a list in TWO launches (``slr_spectral_weight_grad_multi``), each result bit-equal to
+    the per-tensor call.  ``dws[i]`` is the gradient at the effective weight of ``weights[i]`` (= weight_orig, [rows, ...]); its u lies at
+    ``saved_u[offsets[i][0]:]``, its v at ``saved_v[offsets[i][1]:]``, its 1 / sigma at ``inv_sigma[slots[i]]`` (default i): the arrays
+    and offsets ``spectral_sigma`` returns, or any subset of its list.  Returns the list of gradients; ``inplace``: written over ``dws``.
+    The plan is built and uploaded at every call; a network keeps it in a ``SpectralGroup`` (``defer_weight_grad``)."""
+    dws, weights, offsets = list(dws), list(weights), [tuple(int(k) for k in o) for o in offsets]
+    slots = list(range(len(weights))) if slots is None else [int(k) for k in slots]
+    if not weights or not (len(dws) == len(offsets) == len(slots) == len(weights)):
+        raise ValueError("spectral_weight_grad_multi: one dw, one (u_off, v_off) and one slot per weight, at least one weight")
+    for name, t in (("saved_u", saved_u), ("saved_v", saved_v), ("inv_sigma", inv_sigma)):
+        _require("spectral_weight_grad_multi", t, what=name)
+        if t.dim() != 1:
+            raise ValueError(f"spectral_weight_grad_multi: {name} is one-dimensional, got {tuple(t.shape)}")
+    device = saved_u.device
+    for w, dw, (u_off, v_off), k in zip(weights, dws, offsets, slots):
+        _require("spectral_weight_grad_multi", w, what="weight_orig")
+        if w.dim() < 2 or w.numel() == 0:
+            raise ValueError(f"spectral_weight_grad_multi: weight_orig [rows, ...] with at least two dimensions required, got {tuple(w.shape)}")
+        _require("spectral_weight_grad_multi", dw, w.shape, "dw")
+        rows = w.shape[0]
+        if not (0 <= u_off <= saved_u.numel() - rows and 0 <= v_off <= saved_v.numel() - w.numel() // rows and 0 <= k < inv_sigma.numel()):
+            raise ValueError(f"spectral_weight_grad_multi: offsets ({u_off}, {v_off}) / slot {k} outside the saved arrays")
+        if not (w.device == dw.device == device == saved_v.device == inv_sigma.device):
+            raise ValueError("spectral_weight_grad_multi: every tensor lives on one device")
+    outs = dws if inplace else [torch.empty_like(dw) for dw in dws]
+    plan, host, n_work = _grad_plan(dws, weights, outs, offsets, slots, device)
+    call("slr_spectral_weight_grad_multi", device, plan, len(weights), n_work, inv_sigma, saved_u, saved_v)
+    return outs
+
+
 class Normalised:
     """What an operator needs of its weight's normalisation in one forward: ``scale`` (1 / sigma), ``u`` and ``v`` (the constants of the
     backward; None: the plain gradient times scale), the prepared forward / backward fragment buffers (None: made by the single-tensor
-    entries when they are needed) -- tensors or device addresses -- and ``keep``, whatever owns the memory behind the addresses."""
-    __slots__ = ("scale", "u", "v", "fwd", "bwd", "keep")
+    entries when they are needed) -- tensors or device addresses -- and ``keep``, whatever owns the memory behind the addresses.
+    ``weight``: None, or under a group's deferred gradient the alias of ``weight_orig`` the layer computes with -- its gradient is the
+    raw one at the effective weight, and the group turns every layer's into the gradient to ``weight_orig`` at once."""
+    __slots__ = ("scale", "u", "v", "fwd", "bwd", "keep", "weight")
 
-    def __init__(self, scale, u=None, v=None, fwd=None, bwd=None, keep=None):
-        self.scale, self.u, self.v, self.fwd, self.bwd, self.keep = scale, u, v, fwd, bwd, keep
+    def __init__(self, scale, u=None, v=None, fwd=None, bwd=None, keep=None, weight=None):
+        self.scale, self.u, self.v, self.fwd, self.bwd, self.keep, self.weight = scale, u, v, fwd, bwd, keep, weight
 
     def __deepcopy__(self, memo):                        # one forward's state does not travel with a copied or saved module
         return None
@@ -114,6 +171,8 @@ class Normalised:
 
     def weight_grad(self, dw, weight):
         """The gradient to ``weight`` (= weight_orig) from the gradient ``dw`` at the effective weight."""
+        if self.weight is not None:
+            return dw                                    # (deferred: ``weight`` is the group's alias, the group's backward does the rest)
         if self.u is None:
             return dw * self.scale                       # (scale alone: the functional form with a tensor; a constant factor)
         return _weight_grad(dw, weight, self.u, self.v, self.scale)
@@ -164,7 +223,8 @@ class SpectralLinear(nn.Module):
         make_spectral(self)
 
     def forward(self, x):
-        return F.linear(x, _EffectiveWeight.apply(self.weight_orig, take(self)))
+        w, sn = taken(self)
+        return F.linear(x, _EffectiveWeight.apply(w, sn))
 
 
 class UnusedSpectralConv(nn.Module):
@@ -200,6 +260,52 @@ def take(leaf):
         sn = leaf._sn
     object.__setattr__(leaf, "_sn", None)
     return sn
+
+
+def taken(leaf):
+    """(the tensor the layer computes with, ``take(leaf)``): ``weight_orig``, or its alias under a deferred gradient."""
+    sn = take(leaf)
+    return (leaf.weight_orig if sn.weight is None else sn.weight), sn
+
+
+def defer_weight_grad(module, on=True):
+    """Opt-in: the group of ``module`` (a network, or whatever runs its own group) computes the gradients to every ``weight_orig`` of one
+    forward in ONE ``slr_spectral_weight_grad_multi`` (two launches) when that forward's backward is complete, instead of two launches
+    per layer.  The same bits as without it.  Off: exactly the per-layer path."""
+    object.__setattr__(module, "_sn_defer", bool(on))     # (kept on the module: a copied module makes a new group and stays as it was)
+    return module
+
+
+class _DeferredGrad(torch.autograd.Function):
+    """The hook at the end of one forward's backward: the inputs are the ``weight_orig`` of a group's leaves, the outputs aliases of
+    them that the layers compute with.  Autograd calls the backward once every consumer of the aliases has run, with the raw gradient at
+    each effective weight (None: a leaf this forward did not use, which gets no gradient)."""
+
+    @staticmethod
+    def forward(ctx, group, state, *weights):
+        ctx.group, ctx.state = group, state
+        ctx.set_materialize_grads(False)                 # (an alias nothing consumed arrives as None, not as zeros)
+        ctx.save_for_backward(*weights)
+        return tuple(w.detach() for w in weights)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        weights = ctx.saved_tensors
+        used = tuple(i for i, g in enumerate(gs) if g is not None and ctx.needs_input_grad[2 + i])
+        out = [None] * len(gs)
+        if used:
+            dws = []
+            for i in used:
+                g = gs[i].contiguous()
+                _require("SpectralGroup", g, weights[i].shape, "gradient at the effective weight")
+                dws.append(g)
+            # In place over the gradients autograd handed in, against its general rule: an alias is an output of this node with exactly
+            # one consumer (a layer takes its Normalised once per run), so the incoming tensor is that layer's fresh dW (or autograd's
+            # own sum), which nothing else holds -- the aliases are internal: no hook, no retain_grad, no create_graph reaches them.
+            ctx.group._weight_grads(ctx.state, used, dws, [weights[i] for i in used])
+            for i, g in zip(used, dws):
+                out[i] = g
+        return (None, None, *out)
 
 
 def group_of(module):
@@ -353,7 +459,13 @@ class SpectralGroup:
         self.leaves = leaves_of(self.modules)
         self.convs = [m for m in self.leaves if m.weight_orig.dim() == 4]
         self._key, self._plan, self._free, self._eval = None, None, [], None
+        self._grad_plans = {}                            # the plans of the list-wide gradient (deferred mode) by address tuple
         self._layout()
+
+    @property
+    def deferred(self):
+        """``defer_weight_grad`` of the module the group was made for."""
+        return bool(self.modules[0].__dict__.get("_sn_defer", False))
 
     def _layout(self):
         u_off = v_off = 0
@@ -384,8 +496,11 @@ class SpectralGroup:
     def _sigma_plan(self, device):
         return _sigma_plan([(m.weight_orig, m.weight_u, m.weight_v) for m in self.leaves], device)
 
-    @torch.no_grad()
     def run(self):
+        return self._run(torch.is_grad_enabled())
+
+    @torch.no_grad()
+    def _run(self, grad):
         device = self._check()
         tensors = self.tensors()
         key = tuple(t.data_ptr() for t in tensors)
@@ -412,20 +527,40 @@ class SpectralGroup:
             if bufs is not None:
                 call("slr_conv_prep_scaled_multi", device, bufs.plan, bufs.n, bufs.n_work, state.inv_sigma)
             self._eval = None if training else (tuple(t._version for t in tensors), state)
-        self._hand_out(state)
+        self._hand_out(state, grad)
         return state
 
-    def _hand_out(self, state):
+    def _hand_out(self, state, grad=False):
         s0, u0, v0 = state.inv_sigma.data_ptr(), state.saved_u.data_ptr(), state.saved_v.data_ptr()
         P = ctypes.c_void_p
         k = 0
+        alias = [None] * len(self.leaves)
+        if self.deferred and grad and any(m.weight_orig.requires_grad for m in self.leaves):
+            with torch.enable_grad():
+                alias = _DeferredGrad.apply(self, state, *(m.weight_orig for m in self.leaves))
         for i, (m, (u_off, v_off, _, _)) in enumerate(zip(self.leaves, self.offsets)):
             if m.weight_orig.dim() == 4:
-                sn = Normalised(P(s0 + 4 * i), P(u0 + 4 * u_off), P(v0 + 4 * v_off), P(state.bufs.addr[2 * k]), P(state.bufs.addr[2 * k + 1]), state)
+                sn = Normalised(P(s0 + 4 * i), P(u0 + 4 * u_off), P(v0 + 4 * v_off), P(state.bufs.addr[2 * k]), P(state.bufs.addr[2 * k + 1]), state,
+                                alias[i])
                 k += 1
             else:                                                              # a linear: torch multiplies by the scale
-                sn = Normalised(state.inv_sigma[i:i + 1], P(u0 + 4 * u_off), P(v0 + 4 * v_off), keep=state)
+                sn = Normalised(state.inv_sigma[i:i + 1], P(u0 + 4 * u_off), P(v0 + 4 * v_off), keep=state, weight=alias[i])
             object.__setattr__(m, "_sn", sn)
+
+    GRAD_PLANS_MAX = 8                                   # (a forward used twice before its backward, a few address patterns of the allocator)
+
+    def _weight_grads(self, state, used, dws, weights):
+        """In place over ``dws`` (leaf ``used[k]``'s raw gradient): the gradients to ``weight_orig`` with ``state``'s u, v and 1 / sigma,
+        in one ``slr_spectral_weight_grad_multi``.  A plan is uploaded only for a set of leaves and addresses not seen before."""
+        device = state.inv_sigma.device
+        key = (used, tuple(t.data_ptr() for t in dws), tuple(t.data_ptr() for t in weights))
+        plan = self._grad_plans.pop(key, None)
+        if plan is None:
+            while len(self._grad_plans) >= self.GRAD_PLANS_MAX:
+                self._grad_plans.pop(next(iter(self._grad_plans)))            # (the oldest: its memory returns stream-ordered)
+            plan = _grad_plan(dws, weights, dws, [self.offsets[i][:2] for i in used], list(used), device)
+        self._grad_plans[key] = plan                                           # (most recently used last)
+        call("slr_spectral_weight_grad_multi", device, plan[0], len(used), plan[2], state.inv_sigma, state.saved_u, state.saved_v)
 
 
 # --------------------------------------------------------------------------- checkpoints of the reference, unfolded

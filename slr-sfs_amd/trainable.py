@@ -295,7 +295,8 @@ class TrainableConv3x3(nets.Conv):
 
     def forward(self, x, in_b8=False, out_b8=False, residual=None):
         if self.spectral:
-            return conv3x3(x, self.weight_orig, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self, _sn=_spectral.take(self))
+            w, sn = _spectral.taken(self)
+            return conv3x3(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self, _sn=sn)
         return conv3x3(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self)
 
 
@@ -308,8 +309,8 @@ class TrainablePartialConv3x3(nets.PartialConv):
 
     def forward(self, xm, mask, residual=None, in_b8=False, out_b8=False):
         if self.spectral:
-            return partial_conv3x3(xm, mask, self.weight_orig, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self,
-                                   _sn=_spectral.take(self))
+            w, sn = _spectral.taken(self)
+            return partial_conv3x3(xm, mask, w, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
         return partial_conv3x3(xm, mask, self.weight, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self)
 
 
@@ -516,7 +517,8 @@ class TrainableConv1x1(nets.Conv):
 
     def forward(self, x, in_b8=False, out_b8=False):
         if self.spectral:
-            return conv1x1(x, self.weight_orig, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=_spectral.take(self))
+            w, sn = _spectral.taken(self)
+            return conv1x1(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
         return conv1x1(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self)
 
 
@@ -753,8 +755,8 @@ class TrainablePconvInputBlock(TrainablePconvResBlock):
         b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
         n1, n2 = noise if noise is not None else (None, None)
         a, _, _, msum, xs = self.bn1(x, None, n1, b8=b8_in, fork=True, nonzero=True)             # blocks.py:225-231
-        a, m = partial_conv3x3_counts(a, msum, _w(self.conv_aa), self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa,
-                                      _sn=_spectral.take(self.conv_aa) if self.spectral else None)
+        w, sn = _spectral.taken(self.conv_aa) if self.spectral else (self.conv_aa.weight, None)
+        a, m = partial_conv3x3_counts(a, msum, w, self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa, _sn=sn)
         a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238 -- the mask is channel-uniform from here
         skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs
         a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)

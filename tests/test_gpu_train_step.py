@@ -1,0 +1,438 @@
+"""The training iteration on the device: ``slr_sfs_amd.TrainingModel`` and ``slr_sfs_amd.Trainer`` at the shape of
+tests/golden/train_step_vs_reference.npz (batch 2, 32 x 32, the narrow widths of tests/test_gpu_spectral.py, ndf 8, the seeded VGG19 of
+tests/losses_fixture.py, the reference's own noise, two different time pairs).
+
+  * the forward: every loss entry, PredImg and Z_f against the float64 definition of tests/train_step_f64.py (which
+    tests/test_train_step_host.py pins to the reference's own run), criterion E_gpu <= 10 E_plain32 + 1e-6;
+  * one iteration through ``Trainer`` against the SAME iteration written out here from the public pieces (encoder twice,
+    TrainingSynthesis, decoder, tanh, SynthesisLoss, DiscriminatorLoss, Adam): every gradient before each step, every parameter, every
+    u / v / batch-norm buffer and every optimiser state afterwards BIT-equal -- with the deferred list-wide weight gradient on and off,
+    with and without the discriminator, and accumulating over num_steps = 2.  (No float64 comparison of whole-model gradients: each
+    piece's own tests hold its gradient at fixed ReLU / sign / pool decisions, thousands of which sit in this chain.)
+  * isval, a second identical run, no host synchronisation in a whole call, bad batches.
+
+One result in the chain is NOT the same from run to run: the forward of ``splat_blend`` sums each tile's sources in the order its bin
+lists were filled (csrc/blend.hip: "the same from run to run given the same forward result"; include/slr_splat.h: the front ends
+"agree to rounding").  Measured here, two identical forwards differ by up to 9.5e-7 in the blended features and 4.3e-6 in PredImg, and
+every gradient behind them in its last digits.  Bit-equality of two WHOLE iterations is therefore not a property of the package, with
+or without this trainer.  ``_SameSplat`` makes the comparisons exact all the same, and asks no less of everything else: the runs that
+are compared take the raw result of each ``splat_blend`` forward (output and normaliser) from the first of them, and it is asserted
+afterwards that every such call received bit-identical inputs -- so the encoders, the operator's backward, the decoder, the losses, the
+discriminator, both optimiser steps and the weight-gradient pair are all compared bit for bit, on one forward splat result."""
+import functools
+
+import pytest
+import torch
+
+import conv_train_f64 as C64
+import losses_fixture as LF
+import train_step_f64 as T
+from test_gpu_spectral import DEV, _no_sync, held
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def S():
+    import slr_sfs_amd
+    slr_sfs_amd._lib.lib()
+    return slr_sfs_amd
+
+
+@functools.lru_cache(maxsize=None)
+def _fixture():
+    g = T.load()
+    return g, T.state_dict(g), T.forward(g, torch.float64), T.forward(g, torch.float32)
+
+
+def _vgg(S):
+    return S.losses.load_vgg19_state_dict(S.losses.VGG19Features(), LF.vgg19_state_dict()).to(DEV)
+
+
+def _batches(n=1):
+    """The fixture's batch and, for accumulation, a second one (start and end exchanged, the motion reversed, other indices)."""
+    g = _fixture()[0]
+    img = [torch.from_numpy(g["images"][k]).to(DEV) for k in range(3)]
+    motion, index = torch.from_numpy(g["motions"]).to(DEV), torch.from_numpy(g["index"]).to(DEV)
+    nz = {k: [tuple(t.to(DEV) for t in pair) for pair in v] for k, v in T.noise_lists(g).items()}
+    out = [{"images": img, "motions": motion, "index": index, "noise": nz}]
+    if n > 1:
+        nz2 = {"start": nz["end"], "end": nz["start"], "projector": [(b, a) for a, b in nz["projector"]]}
+        out.append({"images": [img[2], img[0], img[1]], "motions": (-motion).contiguous(), "index": [index[:, 0], index[:, 1] + 2, index[:, 2] + 5],
+                    "noise": nz2})
+    return out
+
+
+def _trainer(S, use_d=True, deferred=True):
+    opts = T.options(discriminator_losses="pix2pixHD" if use_d else "0")
+    model = S.TrainingModel(opts, _vgg(S), encoder_widths=T.ENC_WIDTHS, decoder_widths=T.DEC_WIDTHS, decoder_updown=T.UPDOWN)
+    torch.manual_seed(11)                                # (the discriminator's initialisation: the same in the hand-written iteration)
+    trainer = S.Trainer(model, opts).to(DEV).train()
+    model.load_reference_state_dict(_fixture()[1])
+    model.defer_weight_grad(deferred)
+    return trainer
+
+
+SPLAT_CEILING = 1e-5        # float32 rounding of sums of O(1) features in another order; measured: 9.5e-7
+
+
+class _SameSplat:
+    """Inside: the n-th ``splat_blend`` forward returns the output and normaliser that the n-th call of the first run under ``tag``
+    computed (its own kernels still run; their result, equal up to summation order, is replaced before anything reads it).
+    ``verify()``, outside any no-sync region: every replayed call had bit-identical inputs; returns the largest replaced difference."""
+    recorded = {}
+
+    def __init__(self, tag):
+        self.tag, self.n, self.pending = tag, 0, []
+
+    def __enter__(self):
+        from slr_sfs_amd import training
+        self.cls, self.real, me = training._SplatBlend, training._SplatBlend.forward, self
+
+        def forward(ctx, *args):
+            out, norm = me.real(ctx, *args)
+            key, me.n = (me.tag, me.n), me.n + 1
+            ins = [a.detach().clone() for a in args if torch.is_tensor(a)]
+            if key in _SameSplat.recorded:
+                first_ins, o, nrm = _SameSplat.recorded[key]
+                me.pending.append((first_ins, ins, (out.detach() - o).abs().max()))
+                out.data.copy_(o)                        # (.data: the tensors autograd saved keep their version)
+                norm.data.copy_(nrm)
+            else:
+                _SameSplat.recorded[key] = (ins, out.detach().clone(), norm.detach().clone())
+            return out, norm
+        self.cls.forward = staticmethod(forward)
+        return self
+
+    def __exit__(self, *exc):
+        self.cls.forward = staticmethod(self.real)
+        return False
+
+    def verify(self):
+        worst = 0.0
+        for first, now, diff in self.pending:
+            assert len(first) == len(now) and all(torch.equal(a, b) for a, b in zip(first, now)), "a replayed splat_blend had other inputs"
+            worst = max(worst, float(diff))
+        # what is replaced differs from what the run computed by summation order only: float32 rounding of O(1) features.  A forward
+        # that diverged for another reason must not hide behind the replacement.
+        assert worst <= SPLAT_CEILING, f"two forwards of splat_blend on identical inputs differ by {worst:.3e}"
+        return worst
+
+
+# ------------------------------------------------------------------ the forward against float64
+
+def test_forward_against_float64_and_the_reference(S):
+    g, _, r64, r32 = _fixture()
+    trainer = _trainer(S)
+    batch = _batches()[0]
+    torch.cuda.synchronize()
+    with _no_sync(), _SameSplat("forward"):
+        loss, pred = trainer.model(batch)
+    assert sorted(loss) == list(g["loss_keys"]) and sorted(pred) == list(g["pred_keys"])
+    for k in g["loss_keys"]:
+        held("loss " + k, loss[k].detach().cpu().reshape(1), r64["loss"][k].reshape(1), r32["loss"][k].reshape(1))
+        e_ref = C64.E(torch.from_numpy(g["loss/" + k]).reshape(1).double(), r64["loss"][k].reshape(1))
+        print(f"     the reference's own float32 value: E {e_ref:.3e}")
+    held("PredImg", pred["PredImg"].detach().cpu(), r64["PredImg"], r32["PredImg"])
+    held("Z_f", pred["Z_f"].cpu(), r64["Z_f"], r32["Z_f"])
+    assert not pred["Z_f"].requires_grad and pred["PredImg"].requires_grad
+    assert torch.equal(pred["OutputImg"], batch["images"][1]) and torch.equal(pred["GTMotion"], batch["motions"])
+    enc = trainer.model.encoder.blocks[3].conv_aa                                                   # u and v moved twice: start, then end
+    held("encoder u after two calls", enc.weight_u.cpu(), r64["encoder_uv"][3]["w_aa"][0], r32["encoder_uv"][3]["w_aa"][0])
+    # the list form of the index (the [B,3] tensor is the fixture's; a [3] tensor serves a batch of one, as in the reference), and the
+    # three-channel motion (uvm: flow = m[:, :2] * m[:, 2:3])
+    index = batch["index"]
+    m3 = torch.cat([batch["motions"] * 2.0, torch.full_like(batch["motions"][:, :1], 0.5)], 1)
+    for form in (dict(index=[index[:, 0], index[:, 1], index[:, 2]]), dict(index=(index[:, 0], index[:, 1], index[:, 2])), dict(motions=m3)):
+        with _SameSplat("forward") as same:
+            other = _trainer(S).model(dict(batch, **form))
+        print(f"{list(form)}: run-to-run difference of the forward splat that was replaced: {same.verify():.3e}")
+        assert torch.equal(other[1]["PredImg"], pred["PredImg"]) and torch.equal(other[0]["Total Loss"], loss["Total Loss"]), list(form)
+
+
+# ------------------------------------------------------------------ one iteration, by hand and through Trainer
+
+def _snapshot(named):
+    return {k: (None if t is None else t.detach().clone()) for k, t in named}     # (on the device: a copy to the host would synchronise)
+
+
+def _by_hand(S, use_d, batches):
+    with _SameSplat(("iteration", use_d, len(batches))) as same:
+        out = _by_hand_(S, use_d, batches)
+    same.verify()
+    return out
+
+
+def _by_hand_(S, use_d, batches):
+    """base_model.py:95-163 written out from the public pieces, the per-layer weight gradient (no deferred mode)."""
+    from slr_sfs_amd import spectral
+    from slr_sfs_amd.training import TrainingSynthesis
+    opts = T.options(discriminator_losses="pix2pixHD" if use_d else "0")
+    sd = _fixture()[1]
+    enc = S.TrainableEncoderWithZ(cin=3, feat=T.FEAT, widths=T.ENC_WIDTHS, spectral=True).to(DEV).train()
+    dec = S.TrainableDecoderPconv2(cin=T.FEAT, cout=3, widths=T.DEC_WIDTHS, updown=T.UPDOWN, spectral=True).to(DEV).train()
+    spectral.load_spectral_state_dict(enc, sd, "model.module.encoder.")
+    spectral.load_spectral_state_dict(dec, sd, "model.module.projector.")
+    synthesis, loss_fn = TrainingSynthesis(opts), S.losses.SynthesisLoss(opts, _vgg(S))
+    g_params = [p for net in (enc, dec) for p in net.parameters() if p.requires_grad]
+    betas = (opts.beta1, opts.beta2) if use_d else (0.99, opts.beta2)
+    opt_g = S.optim.Adam(g_params, lr=opts.lr_g, betas=betas)
+    if use_d:
+        torch.manual_seed(11)
+        netD = S.DiscriminatorLoss(gan_mode="hinge", lambda_feat=10.0, no_ganFeat_loss=False, ndf=T.NDF, output_nc=3).to(DEV).train()
+        opt_d = S.optim.Adam(list(netD.parameters()), lr=opts.lr_d, betas=betas)
+
+    def forward(b):
+        start, middle, end = b["images"]
+        s_fs, z_f = enc(start, noise=b["noise"]["start"])
+        e_fs, z_p = enc(end, noise=b["noise"]["end"])
+        index = b["index"]
+        idx = index if isinstance(index, list) else [index[:, 0], index[:, 1], index[:, 2]]
+        gen = synthesis(s_fs, z_f, e_fs, z_p, b["motions"], *idx)
+        pred = torch.tanh(dec(gen.contiguous(), noise=b["noise"]["projector"]))
+        return loss_fn(pred, middle), pred, middle
+
+    weight = 1.0 / float(len(batches))
+    opt_g.zero_grad()
+    kept = []
+    for b in batches:
+        t_losses, pred, middle = forward(b)
+        if use_d:
+            g_losses = netD.run_generator_one_step(pred, middle)
+            (g_losses["Total Loss"] / weight + t_losses["Total Loss"] / weight).mean().backward()
+        else:
+            (t_losses["Total Loss"] / weight).mean().backward()
+        kept.append((pred, middle))
+    names = {"model.module.encoder." + k: t for k, t in spectral._entries(enc).items()}
+    names.update({"model.module.projector." + k: t for k, t in spectral._entries(dec).items()})
+    out = {"grads_G": _snapshot((k, t.grad) for k, t in names.items() if t.requires_grad)}
+    opt_g.step()
+    if use_d:
+        opt_d.zero_grad()
+        for pred, middle in kept:
+            d_losses = netD.run_discriminator_one_step(pred, middle)
+            (d_losses["Total Loss"] / weight).mean().backward()
+        out["grads_D"] = _snapshot(("netD." + k, p.grad) for k, p in netD.named_parameters())
+        opt_d.step()
+        names.update({"netD." + k: t for k, t in netD.state_dict().items()})
+        out["state_D"] = {"netD." + k: _snapshot(opt_d.state[p].items()) for k, p in netD.named_parameters()}
+        out["losses"] = _snapshot(list(t_losses.items()) + [(k, v) for d in (g_losses, d_losses) for k, v in d.items() if k != "Total Loss"])
+    else:
+        out["losses"] = _snapshot(t_losses.items())
+    out["tensors"] = _snapshot(names.items())
+    out["state_G"] = {k: _snapshot(opt_g.state[t].items()) for k, t in names.items() if t.requires_grad and not k.startswith("netD.")}
+    out["pred"] = kept[-1][0].detach()
+    return out
+
+
+def _through_trainer(S, use_d, deferred, batches, no_sync=False, tag="iteration"):
+    trainer = _trainer(S, use_d, deferred)
+    same = _SameSplat((tag, use_d, len(batches)))
+    opt = trainer.optimizers
+    out = {}
+
+    def recording(optimizer, key, named):
+        step = optimizer.step
+
+        def wrapped(*a, **k):
+            out[key] = _snapshot(named())
+            return step(*a, **k)
+        optimizer.step = wrapped
+    gen = lambda: {"model.module." + k: t for k, t, learns in trainer.model.reference_parameters() if learns}          # noqa: E731
+    recording(opt.optimizer_G, "grads_G", lambda: ((k, t.grad) for k, t in gen().items()))
+    if use_d:
+        recording(opt.optimizer_D, "grads_D", lambda: (("netD." + k, p.grad) for k, p in trainer.netD.named_parameters()))
+    from slr_sfs_amd import spectral
+    calls, real_call = {}, spectral.call
+
+    def counting(name, *a):
+        calls[name] = calls.get(name, 0) + 1
+        return real_call(name, *a)
+    spectral.call = counting
+    torch.cuda.synchronize()
+    try:
+        if no_sync:
+            with _no_sync(), same:
+                losses, images = trainer(iter(batches), num_steps=len(batches))
+        else:
+            with same:
+                losses, images = trainer(iter(batches), num_steps=len(batches))
+    finally:
+        spectral.call = real_call
+    # which gradient entry point ran: the list-wide pair once per group run (encoder twice, decoder once) and the per-tensor one never,
+    # or the per-tensor one for every normalised tensor of every run and the list-wide one never
+    enc, dec = (len(spectral.group_of(net).leaves) for net in (trainer.model.encoder, trainer.model.projector))
+    multi, single = calls.get("slr_spectral_weight_grad_multi", 0), calls.get("slr_spectral_weight_grad", 0)
+    assert (multi, single) == ((3 * len(batches), 0) if deferred else (0, (2 * enc + dec) * len(batches))), (deferred, multi, single, enc, dec)
+    assert bool(spectral.group_of(trainer.model.encoder)._grad_plans) == bool(spectral.group_of(trainer.model.projector)._grad_plans) == deferred
+    out["gradient_calls"] = (multi, single)
+    out["splat_difference"] = same.verify()
+    sd = trainer.reference_state_dict()
+    out["tensors"] = {k: v for k, v in sd.items() if "loss_function" not in k and k.split(".")[-1] not in ("min_z", "max_z", "discretized_zs")}
+    out["state_G"] = {k: _snapshot(opt.optimizer_G.state[t].items()) for k, t in gen().items()}
+    if use_d:
+        out["state_D"] = {"netD." + k: _snapshot(opt.optimizer_D.state[p].items()) for k, p in trainer.netD.named_parameters()}
+    out["losses"] = _snapshot(losses.items())
+    out["images"] = images
+    return out
+
+
+def _same(a, b, what):
+    assert sorted(a) == sorted(b), (what, sorted(set(a) ^ set(b))[:6])
+    for k in a:
+        if isinstance(a[k], dict):
+            _same(a[k], b[k], f"{what} {k}")
+        else:
+            assert (a[k] is None) == (b[k] is None), (what, k)
+            assert a[k] is None or torch.equal(a[k], b[k]), (what, k)
+
+
+def _compare(hand, got, use_d):
+    for part in ("grads_G", "tensors", "state_G", "losses") + (("grads_D", "state_D") if use_d else ()):
+        _same(hand[part], got[part], part)
+    assert all(g is not None for g in hand["grads_G"].values())
+    # normalize_image: the returned images are 0.5 x + 0.5 of the model's
+    assert torch.equal(got["images"]["PredImg"].detach(), 0.5 * hand["pred"] + 0.5)
+
+
+@functools.lru_cache(maxsize=None)
+def _hand_cached(use_d, steps):
+    import slr_sfs_amd
+    return _by_hand(slr_sfs_amd, use_d, _batches(steps))
+
+
+@pytest.mark.parametrize("deferred", [False, True], ids=["per-layer", "deferred"])
+@pytest.mark.parametrize("use_d", [True, False], ids=["with-D", "without-D"])
+def test_one_iteration_has_the_bits_of_the_hand_written_one(S, use_d, deferred):
+    hand = _hand_cached(use_d, 1)
+    got = _through_trainer(S, use_d, deferred, _batches(1))
+    _compare(hand, got, use_d)
+    moved = sum(1 for k, v in hand["tensors"].items() if k in _fixture()[1] and not torch.equal(v.cpu(), _fixture()[1][k]))
+    print(f"D {use_d} deferred {deferred}: {len(hand['grads_G'])} generator gradients, {len(hand['tensors'])} tensors ({moved} moved), "
+          f"{len(hand['state_G'])} optimiser states bit-equal; losses {sorted(hand['losses'])}")
+    assert moved > len(hand["grads_G"])                  # parameters, u, v and the batch-norm statistics all moved
+    if use_d:
+        assert sorted(hand["losses"]) == ["D_Fake", "D_real", "GAN", "GAN_Feat", "L1", "Perceptual", "Total Loss", "psnr", "ssim"]
+
+
+def test_two_steps_accumulate_like_the_hand_written_loop(S):
+    hand = _hand_cached(True, 2)
+    got = _through_trainer(S, True, True, _batches(2))
+    _compare(hand, got, True)
+    one = _hand_cached(True, 1)
+    assert not torch.equal(hand["grads_G"]["model.module.projector.eblocks.7.conv_ab.weight_orig"],
+                           one["grads_G"]["model.module.projector.eblocks.7.conv_ab.weight_orig"])
+
+
+def test_second_run_same_bits_and_nothing_synchronises(S):
+    a = _through_trainer(S, True, True, _batches(1), no_sync=True, tag="twice")
+    b = _through_trainer(S, True, True, _batches(1), no_sync=True, tag="twice")
+    print(f"the forward splat of the second run differed from the first by {b['splat_difference']:.3e} before it was replaced")
+    for part in ("grads_G", "grads_D", "tensors", "state_G", "state_D", "losses"):
+        _same(a[part], b[part], part)
+    c = _through_trainer(S, False, True, _batches(2), no_sync=True, tag="short")          # the shorter branch, accumulating
+    assert all(torch.isfinite(v).all() for v in c["losses"].values())
+
+
+def test_isval_is_a_forward_only(S):
+    trainer, twin = _trainer(S), _trainer(S)
+    batch = _batches()[0]
+    before = trainer.reference_state_dict()
+    torch.cuda.synchronize()
+    with _no_sync(), _SameSplat("isval"):
+        losses, images, back = trainer(iter([batch]), isval=True, return_batch=True)
+    assert back is batch and trainer._optimizers is None                      # no optimiser was even made
+    with _SameSplat("isval") as same:
+        t_losses, t_images = twin.model(batch)                                # what a train()-mode forward does, and no more
+    same.verify()
+    after, ref = trainer.reference_state_dict(), twin.reference_state_dict()
+    assert all(torch.equal(after[k], ref[k]) for k in ref)
+    learn = {"model.module." + k for k, _, l in trainer.model.reference_parameters() if l} | {k for k in before if k.startswith("netD.")}
+    assert all(torch.equal(after[k], before[k]) for k in learn)               # no parameter moved
+    assert any(not torch.equal(after[k], before[k]) for k in before if k.endswith("weight_u"))
+    assert all(p.grad is None for p in trainer.parameters())
+    assert torch.equal(images["PredImg"], 0.5 * t_images["PredImg"] + 0.5) and torch.equal(images["OutputImg"], 0.5 * batch["images"][1] + 0.5)
+    assert torch.equal(images["Z_f"], t_images["Z_f"]) and torch.equal(losses["Total Loss"], t_losses["Total Loss"])
+
+
+def test_checkpoint_with_optimisers_round_trips(S):
+    a = _trainer(S)
+    a(iter(_batches(1)))
+    ckpt = a.reference_checkpoint()
+    assert set(ckpt) == {"state_dict", "optimizerG", "optimizerD"}
+    n_ref = len(_fixture()[0]["parameter_order"])
+    assert ckpt["optimizerG"]["param_groups"][0]["params"] == list(range(n_ref))
+    assert all(_fixture()[0]["parameter_learns"][k] for k in ckpt["optimizerG"]["state"])            # the reference's indices: none of a frozen one
+    assert len(ckpt["optimizerG"]["state"]) == sum(l for _, _, l in a.model.reference_parameters())
+    b = _trainer(S, deferred=False)
+    b.load_reference_checkpoint(ckpt)
+    back = b.reference_checkpoint()
+    _same(ckpt["state_dict"], back["state_dict"], "state_dict")
+    for name in ("optimizerG", "optimizerD"):
+        assert back[name]["param_groups"] == ckpt[name]["param_groups"]
+        _same({k: _snapshot(st.items()) for k, st in ckpt[name]["state"].items()}, {k: _snapshot(st.items()) for k, st in back[name]["state"].items()}, name)
+    with _SameSplat("resume"):
+        x = a(iter(_batches(1)))
+    with _SameSplat("resume") as same:
+        y = b(iter(_batches(1)))                                              # and the two go on alike
+    same.verify()
+    assert torch.equal(x[0]["Total Loss"], y[0]["Total Loss"]) and torch.equal(x[1]["PredImg"], y[1]["PredImg"])
+    a.update_learning_rate()
+    assert a.optimizer_G.param_groups[0]["lr"] == pytest.approx(5e-4 - 5e-4 / 10) and a.optimizer_D.param_groups[0]["lr"] == pytest.approx(2e-3 - 2e-3 / 10)
+
+
+def test_the_other_forward_paths(S):
+    """Z_model with relu, train_Z off, and the [3] index tensor of a batch of one."""
+    batch = _batches()[0]
+
+    def model(**more):
+        opts = T.options(**more)
+        m = S.TrainingModel(opts, _vgg(S), encoder_widths=T.ENC_WIDTHS, decoder_widths=T.DEC_WIDTHS, decoder_updown=T.UPDOWN).to(DEV).train()
+        return m.load_reference_state_dict(_fixture()[1])
+    plain, relu, no_z = model(), model(Z_model="encoder_relu"), model(train_Z=False)
+    raw = []
+    hook = relu.encoder.register_forward_hook(lambda mod, a, o: raw.append(o[1].detach().clone()))
+    (l0, p0), (l1, p1), (l2, p2) = plain(batch), relu(batch), no_z(batch)
+    hook.remove()
+    z = torch.relu(raw[0])                                                    # :488-490, then :601-605
+    assert bool((raw[0] < 0).any()) and torch.equal(p1["Z_f"], torch.clamp(z - z.max(), min=-20.0, max=20.0))
+    assert not torch.equal(p1["Z_f"], p0["Z_f"]) and not torch.equal(p1["PredImg"], p0["PredImg"])
+    assert torch.equal(p2["Z_f"], torch.zeros_like(p0["Z_f"])) and not torch.equal(p2["PredImg"], p0["PredImg"])      # ones - max(ones), clamped
+    assert all(bool(torch.isfinite(l[k]).all()) for l in (l1, l2) for k in l)
+    l2["Total Loss"].backward()                                               # train_Z off: the logits get no gradient, the rest does
+    assert no_z.encoder.blocks[0].conv_aa.weight_orig.grad is not None
+    one = {"images": [t[1:2].contiguous() for t in batch["images"]], "motions": batch["motions"][1:2].contiguous(),
+           "noise": {k: [tuple(t[1:2].contiguous() for t in pair) for pair in v] for k, v in batch["noise"].items()}}
+    with _SameSplat("one"):
+        a = model()(dict(one, index=batch["index"][1:2]))                     # [1, 3]
+    with _SameSplat("one") as same:
+        b = model()(dict(one, index=batch["index"][1]))                       # [3]: index[0], index[1], index[2] are 0-d
+    same.verify()
+    assert torch.equal(a[1]["PredImg"], b[1]["PredImg"]) and torch.equal(a[0]["Total Loss"], b[0]["Total Loss"])
+
+
+def test_bad_batches_raise(S):
+    model = _trainer(S).model
+    good = _batches()[0]
+    with pytest.raises(NotImplementedError, match="ROCm device tensors only"):
+        model(dict(good, motions=good["motions"].cpu()))
+    with pytest.raises(NotImplementedError, match="ROCm device tensors only"):
+        model(dict(good, images=[good["images"][0], good["images"][1].cpu(), good["images"][2]]))
+    with pytest.raises(ValueError, match="start, middle, end"):
+        model(dict(good, images=good["images"][:2]))
+    with pytest.raises(ValueError, match="does not match"):
+        model(dict(good, images=[good["images"][0], good["images"][1][:, :, :16], good["images"][2]]))
+    with pytest.raises(ValueError, match="motions"):
+        model(dict(good, motions=good["motions"][:, :, :16].contiguous()))
+    with pytest.raises(ValueError, match="motions"):
+        model(dict(good, motions=torch.cat([good["motions"], good["motions"]], 1)))
+    with pytest.raises(TypeError, match="float32"):
+        model(dict(good, motions=good["motions"].double()))
+    with pytest.raises(ValueError, match="W = 32"):
+        model(dict(good, images=[t[:, :, :16, :16].contiguous() for t in good["images"]], motions=good["motions"][:, :, :16, :16].contiguous()))
+    with pytest.raises(TypeError, match="index"):
+        model(dict(good, index={"start": 0}))
+    with pytest.raises(ValueError, match="index"):
+        model(dict(good, index=[good["index"][:, 0], good["index"][:, 1]]))
+    with pytest.raises(NotImplementedError, match="depth"):
+        model(dict(good, depth=good["images"][0][:, :1]))
