@@ -1,6 +1,10 @@
 """Host-side checks of the list-wide spectral weight gradient (no GPU): ABI 21, the plan of ``slr_spectral_weight_grad_multi`` decoded from
 the layout include/slr_splat.h documents -- work items, offsets, scratch -- for lists of 1 and 130 tensors over the shapes of the sigma
-list, the refusals of the three entry points, and the Python side's refusals and opt-in switch, none of which touches a device."""
+list, the refusals of the three entry points, and the Python side's refusals and opt-in switch, none of which touches a device.  Then the model
+and the trainer: options, keys, the float64 definition of tests/train_step_f64.py pinned to the reference's run, and that definition's
+gradients -- autograd against the written-out backward, the pinned gate-clean case of the tight level, and the deliberately wrong
+compositions that the criterion must tell from float32 rounding at each level."""
+import functools
 import os
 import re
 
@@ -334,3 +338,162 @@ def test_float64_definition_is_pinned_to_the_reference():
         e_ref, e_def = C64.E(ref.double(), d64), C64.E(d32.double(), d64)
         print(f"{name}: E(reference32, def64) {e_ref:.3e}  E(def32, def64) {e_def:.3e}  bound {10 * e_def + 1e-6:.3e}")
         assert e_ref <= 10 * e_def + 1e-6, name
+
+
+# ------------------------------------------------------------------ the float64 definition of the iteration's gradients
+
+@functools.lru_cache(maxsize=None)
+def _g():
+    import train_step_f64 as T
+    return T.load()
+
+
+@functools.lru_cache(maxsize=None)
+def _tight(train_z=True, n=1, mutant=None, dtype=torch.float64):
+    import train_step_f64 as T
+    inputs, gpred = T.clean_batches(_g(), train_z, n)
+    return T.chain_gradients(inputs, gpred, dtype, T.options(W=8, train_Z=train_z), (mutant,) if mutant else (), _g())
+
+
+def _disc_state(seed):
+    """The discriminator's initialisation as tests/test_gpu_train_step.py::_trainer makes it, under disc_f64's keys."""
+    import slr_sfs_amd as S
+    import train_step_f64 as T
+    torch.manual_seed(seed)
+    d = S.DiscriminatorLoss(gan_mode="hinge", lambda_feat=10.0, no_ganFeat_loss=False, ndf=T.NDF, output_nc=3)
+    return {k[len("netD.netD."):]: v.detach().clone() for k, v in d.state_dict().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _loose(use_d=True, n=1, mutant=None, dtype=torch.float64):
+    import train_step_f64 as T
+    one = T.fixture_inputs(_g())
+    return T.iteration_gradients([one, T.second_batch(one)][:n], _disc_state(T.DISC_SEED) if use_d else None, dtype, use_d,
+                                 mutants=(mutant,) if mutant else (), g=_g())
+
+
+def _outside(figs):
+    """(tensors outside their bound, the largest e / bound) of train_step_f64.figures' result."""
+    over = [e / b for e, _, b in figs.values()]
+    return sum(r > 1.0 for r in over), max(over)
+
+
+def test_autograd_is_the_written_out_gradient():
+    """The leaves' gradients that autograd gives the differentiable definition are ``spectral_f64.network_grads``' -- the written-out
+    backward every piece is tested against -- fed with autograd's own gradient at that network's output: the decoder, and the encoder
+    as the sum of its two calls (each with the u, v and sigma of ITS forward), in float64 to 1e-12 of the largest element.  The 16
+    cancelling biases are held against the magnitude of their terms, as everywhere."""
+    import block_train_f64 as B64
+    import conv_train_f64 as C64
+    import spectral_f64 as S64
+    import train_step_f64 as T
+    (inp,), (gpred,) = T.clean_batches(_g())
+    net = T.generator(_g(), torch.float64)
+    f = T.generator_forward(net, inp, torch.float64, T.options(W=8))
+    outs = [call[0][-1]["y"] for call in f["encoder_calls"]] + [f["decoder"][0][-1]["y"]]
+    for y in outs:
+        y.retain_grad()
+    f["PredImg"].backward(gpred.double())
+    assert all(y.grad is not None and bool(y.grad.abs().max() > 0) for y in outs)
+    written = {}
+    with torch.no_grad():
+        runs = [("encoder.gblocks", T.ENC_FORMS, T.ENC_NAMES, net["enc"], [None] * 8, call, y.grad) for call, y in zip(f["encoder_calls"], outs)]
+        runs.append(("projector.eblocks", T.DEC_FORMS, T.DEC_NAMES, net["dec"], T.UPDOWN, f["decoder"], outs[2].grad))
+        for head, forms, names, ps, kinds, (fs, uns, ctxs, noise), gy in runs:
+            ds = S64.network_grads(forms, fs, ps, uns, kinds, noise, gy, ctxs)
+            for i, d in enumerate(ds):
+                for name, key in names.items():
+                    if ps[i].get(name) is None:
+                        continue
+                    rows = [(f"{head}.{i}.{key}.weight_orig", d["d_" + name], None)]
+                    b = T.BIASES.get(name)
+                    if b is not None and ps[i].get(b) is not None:
+                        rows.append((f"{head}.{i}.{key}.bias", d["d" + b], d["db_aa_terms"].max() if b == "b_aa" else None))
+                    for k, t, terms in rows:
+                        old = written.get(k, (0.0, None))
+                        written[k] = (old[0] + t, terms if old[1] is None else old[1] + terms)
+    assert sorted(written) == sorted(net["leaves"]) and len(written) == 141
+    worst = 0.0
+    for k, (t, terms) in written.items():
+        e = C64.E(net["leaves"][k].grad, t) if terms is None else B64.E_terms(net["leaves"][k].grad, t, terms)
+        worst = max(worst, e)
+        assert e <= 1e-12, (k, e)
+    print(f"autograd against the written-out gradient: {len(written)} leaves, largest E {worst:.3e}")
+
+
+def test_the_gate_clean_case_is_pinned():
+    """The small case of the tight level (train_step_f64.clean_case) at its pinned seeds: the margins, that the first seed IS the first,
+    that the Euler integration gives float32 and float64 the same flows, and that the case exercises what it is there for -- pixels
+    leaving the frame in both directions and holes in the blended features, so that the per-element mask of the decoder's first block
+    has something to do."""
+    import train_step_f64 as T
+    assert T.CLEAN_SEEDS[True][0] == 14 and T.MARGIN == 1e-4
+    assert T.first_clean_seed(_g(), T.options(W=8), limit=T.CLEAN_SEEDS[True][0] + 1)[0] == T.CLEAN_SEEDS[True][0]
+    off = T.options(W=8, train_Z=False)                  # train_Z off: both seeds are the first of their searches, below the limit of 200
+    assert T.CLEAN_SEEDS[False] == (52, 82) and max(T.CLEAN_SEEDS[False]) < 200
+    assert T.first_clean_seed(_g(), off, limit=53)[0] == 52
+    assert T.first_clean_seed(_g(), off, before=(T.clean_case(_g(), 52)[0],), limit=83)[0] == 82
+    for train_z in (True, False):
+        r64, r32 = _tight(train_z, 2), _tight(train_z, 2, None, torch.float32)
+        for n, pre in enumerate(r64["pre"]):
+            m = T.margin(pre)
+            print(f"train_Z {train_z} batch {n} seed {T.CLEAN_SEEDS[train_z][n]}: margin {m:.4e} over {len(pre)} batch-norm evaluations, "
+                  f"{r64['holes'][n]} zeros in gen_fs")
+            assert len(pre) == 48 and m > T.MARGIN
+            assert r64["holes"][n] > 0
+            for d in range(2):
+                flow = r64["flows"][n][d]
+                assert torch.equal(flow.float(), r32["flows"][n][d]) and torch.equal(flow.float().double(), flow)
+                gone = flow[:, 0] == 9.0                                      # max(H, W) + 1: the pixel left the frame
+                assert bool(gone.any()) and not bool(gone.all())
+    assert _tight(True, 1)["margin"] == T.margin(_tight(True, 2)["pre"][0])   # (the first batch of two is the single batch)
+
+
+TIGHT_MUTANTS = (("end_dropped", 1), ("through_power", 1), ("first_uv", 1), ("overwrite", 2))
+LOOSE_MUTANTS = (("end_dropped", 1), ("through_power", 1), ("no_gan", 1), ("no_weight", 2), ("stale_d_uv", 1))
+LOOSE_MEASURED_ONLY = (("first_uv", 1), ("overwrite", 2))
+LOOSE_MUTANTS_WITHOUT_D = (("no_weight", 2), ("overwrite", 2))               # the accumulation of the trainer's branch without a discriminator
+
+
+def test_the_tight_criterion_separates_mutants_from_rounding():
+    """At the 8 x 8 case every wrong composition of train_step_f64.MUTANTS' first four leaves 10 E_plain32 + 1e-6 on at least one
+    tensor; the definition's own float32 run, by construction, on none."""
+    import train_step_f64 as T
+    for mutant, n in TIGHT_MUTANTS:
+        r64, r32, bad = _tight(True, n), _tight(True, n, None, torch.float32), _tight(True, n, mutant)
+        figs = T.figures(bad["grads"], r64["grads"], r32["grads"])
+        count, ratio = _outside(figs)
+        print(f"tight, {mutant} ({n} batch): {count} of {len(figs)} tensors outside the bound, by up to {ratio:.1f} x")
+        assert len(figs) == 141 and count >= 1, mutant
+    plain = [e for e, _, _ in T.figures(r32["grads"], r64["grads"], r32["grads"]).values()]
+    print(f"tight: E_plain32 {min(plain):.3e} .. {max(plain):.3e}")
+
+
+def test_the_loose_level_stays_meaningful_and_separates_its_mutants():
+    """At the fixture shape through L1 + VGG and the discriminator: E_plain32 <= 0.03 on every compared tensor (no bound above 0.3) in
+    the four cases the device test runs, and every mutant of the lists out of bound on at least one tensor."""
+    import train_step_f64 as T
+    assert T.SECOND_OFFSETS == (2, 4)
+    for use_d, n in ((True, 1), (False, 1), (True, 2), (False, 2)):
+        r64, r32 = _loose(use_d, n), _loose(use_d, n, None, torch.float32)
+        figs = T.figures(r32["grads_G"], r64["grads_G"], r32["grads_G"])
+        if use_d:
+            figs.update(T.figures(r32["grads_D"], r64["grads_D"], r32["grads_D"], T.final_bias_terms(r64["grads_D"], n)))
+        plain = sorted(e for e, _, _ in figs.values())
+        print(f"loose, D {use_d}, {n} batch: E_plain32 {plain[0]:.3e} .. median {plain[len(plain) // 2]:.3e} .. {plain[-1]:.3e} "
+              f"over {len(figs)} tensors")
+        assert len(figs) == 141 + (14 if use_d else 0) and plain[-1] <= 0.03, (use_d, n, plain[-1])
+    for mutant, n in LOOSE_MUTANTS + LOOSE_MEASURED_ONLY:
+        r64, r32, bad = _loose(True, n), _loose(True, n, None, torch.float32), _loose(True, n, mutant)
+        figs_g = T.figures(bad["grads_G"], r64["grads_G"], r32["grads_G"])
+        figs_d = T.figures(bad["grads_D"], r64["grads_D"], r32["grads_D"], T.final_bias_terms(r64["grads_D"], n))
+        (cg, rg), (cd, rd) = _outside(figs_g), _outside(figs_d)
+        print(f"loose, {mutant} ({n} batch): generator {cg} of {len(figs_g)} outside the bound, by up to {rg:.1f} x; "
+              f"discriminator {cd} of {len(figs_d)}, by up to {rd:.1f} x")
+        if (mutant, n) in LOOSE_MUTANTS:
+            assert cg + cd >= 1, mutant
+    for mutant, n in LOOSE_MUTANTS_WITHOUT_D:
+        r64, r32, bad = _loose(False, n), _loose(False, n, None, torch.float32), _loose(False, n, mutant)
+        count, ratio = _outside(T.figures(bad["grads_G"], r64["grads_G"], r32["grads_G"]))
+        print(f"loose without the discriminator, {mutant} ({n} batch): generator {count} of 141 outside the bound, by up to {ratio:.1f} x")
+        assert count >= 1, mutant
