@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 21
+#define SLR_ABI_VERSION 22
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -291,6 +291,24 @@ int slr_splat_blend_forward(const float *values_f, const float *logits_f, const 
                             const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
                             int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags,
                             void *scratch, size_t scratch_bytes, void *stream);
+
+/* The same with `flags` (slr_splat_blend_forward is this call with flags 0; unknown bits: SLR_E_BADARG before the device is touched).
+ * SLR_BLEND_DETERMINISTIC: tile kernels whose per-pixel record lists are ranked by source pixel instead of taking the order in which the
+ * waves of a workgroup reached an LDS counter -- `out` and `norm` are then a function of the inputs, the shape and the front-end
+ * settings (slr_splat_set_front_end, slr_splat_set_scan_max_tiles; NOT of slr_splat_set_scan_shape's channel groups) alone: the same bits
+ * from run to run, under any load.  One exception, which is counted: a flow with so many pile-ups that a deferred piece of the scan front
+ * end finds no room in the workspace's entry array or no slabs in its pool is rendered another way (still correct, another summation
+ * tree), and WHICH pieces are refused depends on their arrival order.  Every such refusal of a deterministic call increments a 32-bit word
+ * of the splat workspace that is zero after slr_splat_workspace_init and is never reset: the guarantee holds while it reads 0.
+ * slr_splat_fallback_count_offset: the byte offset of that word in a workspace for this shape (0 for a non-positive size; host
+ * arithmetic only) -- read it as a device value, no synchronisation needed to locate it. */
+#define SLR_BLEND_DETERMINISTIC 1
+int slr_splat_blend_forward_ex(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
+                               const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
+                               const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
+                               int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags, int flags,
+                               void *scratch, size_t scratch_bytes, void *stream);
+size_t slr_splat_fallback_count_offset(int N, int H, int W);
 
 /* Its backward for grad_out = dL/dout [N,C,H,W], with `out` and `norm` as the forward wrote them.  Any of the six gradient pointers may
  * be NULL (needs_input_grad); the others are bit-identical to the call that asks for all six.  grad_logits_d needs logits_d; it is

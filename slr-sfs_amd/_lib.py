@@ -7,8 +7,9 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 21
+ABI_VERSION = 22
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
+BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
 # The C ABI of include/slr_splat.h, once: entry point -> (return type, argument types).  lib() applies it; SYMBOLS is its keys.
 _vp, _fp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -45,6 +46,8 @@ SIGNATURES = {
     "slr_softsplat_backward_ws": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_splat_blend_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "slr_splat_blend_forward": (_i, [_fp] * 9 + [_f, _f, _f, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _vp]),
+    "slr_splat_blend_forward_ex": (_i, [_fp] * 9 + [_f, _f, _f, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _i, _vp, _sz, _vp]),
+    "slr_splat_fallback_count_offset": (_sz, [_i, _i, _i]),
     "slr_splat_blend_backward": (_i, [_fp] * 9 + [_f, _f, _f] + [_fp] * 9 + [_i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_maxsplat_forward": (_i, [_fp, _fp, _fp, _f, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
     "slr_max_warp_norm": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _i, _vp]),

@@ -266,7 +266,7 @@ static bool blend_sizes_ok(int N, int C, int H, int W) {
 
 int splat_weighted_sum(const float *values, const float *logits, const float *zmax, const float *alpha, int second, float lo, float hi,
                        const float *flow, float *sum, float *norm, int N, int C, int H, int W, void *ws, size_t ws_bytes, int ws_flags,
-                       hipStream_t st);                              // splat_op.hip
+                       bool det, hipStream_t st);                    // splat_op.hip
 
 }  // namespace slr
 
@@ -278,11 +278,14 @@ SLR_EXPORT size_t slr_splat_blend_ws_bytes(int N, int C, int H, int W) {
     return L.fwd > L.bwd ? L.fwd : L.bwd;
 }
 
-SLR_EXPORT int slr_splat_blend_forward(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
-                                       const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
-                                       const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
-                                       int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags,
-                                       void *scratch, size_t scratch_bytes, void *stream) {
+// flags & SLR_BLEND_DETERMINISTIC: the DET forms of the tile kernels (splat_op.hip) -- blend_normalize_kernel is a fixed order anyway.
+SLR_EXPORT int slr_splat_blend_forward_ex(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
+                                          const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
+                                          const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
+                                          int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags, int flags,
+                                          void *scratch, size_t scratch_bytes, void *stream) {
+    SLR_CHECK_ARG(!(flags & ~SLR_BLEND_DETERMINISTIC), "flags: unknown bits (SLR_BLEND_DETERMINISTIC)");
+    const bool det = (flags & SLR_BLEND_DETERMINISTIC) != 0;
     SLR_CHECK_ARG(values_f && disp_f && values_p && disp_p && alpha && out && norm, "null pointer");
     SLR_CHECK_ARG(blend_sizes_ok(N, C, H, W), "sizes (N, C, H, W > 0, N < 2^15, N*H*W < 2^29, H*W < 2^26)");
     SLR_CHECK_ARG(clamp_lo <= clamp_hi && eps > 0.0f, "clamp range / eps");
@@ -295,13 +298,22 @@ SLR_EXPORT int slr_splat_blend_forward(const float *values_f, const float *logit
     float *sum_f = (float *)scratch, *sum_p = (float *)((char *)scratch + L.stack);
     float *nrm_f = (float *)((char *)scratch + 2 * L.stack), *nrm_p = (float *)((char *)scratch + 2 * L.stack + L.plane);
     if (int e = splat_weighted_sum(values_f, logits_f, logits_f ? zmax_f : nullptr, alpha, 0, clamp_lo, clamp_hi, disp_f, sum_f, nrm_f, N, C, H, W,
-                                   splat_ws, splat_ws_bytes, ws_flags, st)) return e;
+                                   splat_ws, splat_ws_bytes, ws_flags, det, st)) return e;
     if (int e = splat_weighted_sum(values_p, logits_p, logits_p ? zmax_p : nullptr, alpha, 1, clamp_lo, clamp_hi, disp_p, sum_p, nrm_p, N, C, H, W,
-                                   splat_ws, splat_ws_bytes, ws_flags, st)) return e;
+                                   splat_ws, splat_ws_bytes, ws_flags, det, st)) return e;
     hipLaunchKernelGGL(blend_normalize_kernel, dim3((unsigned)(N * L.blocks)), dim3(256), 0, st, (const float *)sum_f, (const float *)sum_p,
                        (const float *)nrm_f, (const float *)nrm_p, out, norm, eps, C, H * W);
     SLR_CHECK_LAUNCH();
     return 0;
+}
+
+SLR_EXPORT int slr_splat_blend_forward(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,
+                                       const float *logits_p, const float *disp_p, const float *alpha, const float *zmax_f,
+                                       const float *zmax_p, float clamp_lo, float clamp_hi, float eps, float *out, float *norm,
+                                       int N, int C, int H, int W, void *splat_ws, size_t splat_ws_bytes, int ws_flags,
+                                       void *scratch, size_t scratch_bytes, void *stream) {
+    return slr_splat_blend_forward_ex(values_f, logits_f, disp_f, values_p, logits_p, disp_p, alpha, zmax_f, zmax_p, clamp_lo, clamp_hi, eps, out, norm,
+                                      N, C, H, W, splat_ws, splat_ws_bytes, ws_flags, 0, scratch, scratch_bytes, stream);
 }
 
 SLR_EXPORT int slr_splat_blend_backward(const float *values_f, const float *logits_f, const float *disp_f, const float *values_p,

@@ -405,7 +405,7 @@ struct OpArgs {
 // rows front end.  grid.x: a multiple of 8 * SLR_XCD_GROUP blocks covering the plan's items (surplus workgroups exit at once).
 // PASSES = false: one piece per workgroup, no loop over work (80 VGPRs: three workgroups per CU); a piece of more than SEG entries is
 // appended to the deferred list.  PASSES = true: OP_DEFER_WG workgroups walk the deferred list pass by pass (normally it is empty).
-template <bool NORM, bool MAXOP, bool PASSES, bool RAW>
+template <bool NORM, bool MAXOP, bool PASSES, bool RAW, bool DET = false>
 __device__ __forceinline__ void op_rows_body(const OpArgs &a) {
     using Cfg = std::conditional_t<PASSES, OpPassCfg, OpCfg>;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -436,13 +436,13 @@ __device__ __forceinline__ void op_rows_body(const OpArgs &a) {
 #ifdef SLR_TRACE
         T_NOTE(s, 58, t_entry);
 #endif
-        if (!rows_piece_once<Cfg, false, NORM, MAXOP, false, RAW>(s, f, L, p, tid, k, cb, ce) && tid == 0 && blockIdx.y == 0)
+        if (!rows_piece_once<Cfg, false, NORM, MAXOP, false, RAW, DET>(s, f, L, p, tid, k, cb, ce) && tid == 0 && blockIdx.y == 0)
             f.defer[atomicAdd(f.totals + 4, 1u)] = at;     // (one entry per piece: every channel group gets here)
         T_NOTE(s, 57, wall_clock64());
     } else {
         const uint32_t ndef = has_planes ? f.totals[4] : 0u;
         for (uint32_t q = blockIdx.x; q < ndef; q += gridDim.x)
-            rows_piece_passes<Cfg, false, NORM, MAXOP, false, RAW>(s, f, L, make_piece<Cfg>(s, f.items[f.defer[q]]), tid, k, cb, ce);
+            rows_piece_passes<Cfg, false, NORM, MAXOP, false, RAW, DET>(s, f, L, make_piece<Cfg>(s, f.items[f.defer[q]]), tid, k, cb, ce);
         // the last workgroup to get here empties the deferred list for the plan's next use (prebinned calls share one plan).  EVERY
         // workgroup of the grid arrives -- also those whose channel group is empty (C = 36, 65, 72, 80 with 8 groups): counting only some
         // of them left the list in place for the next prebinned call, which then walked the same pieces again
@@ -538,7 +538,10 @@ __device__ __forceinline__ uint32_t scan_collect(const TileShared &s, const Tile
 // follows (normally empty) renders it with many workgroups at once.
 // (Measured and rejected in rounds 4 / 5: the deferred pieces as TAIL blocks of the same launch behind an arrival counter -- config C2
 //  37 -> 49.5 us, 512 arrival atomics on one word ~ 20 us; column pieces in the first launch: every piece repeats the candidate walk.)
-template <bool NORM, bool MAXOP, bool RAW>
+// DET: canonical record lists (build_records); a deferred piece that is refused room in the entry array or slabs in the pool -- which
+// of the call's pieces that happens to depends on the order in which they reach the two counters -- is counted in the workspace's
+// sticky fallback word (totals[DET_FALLBACK_WORD]: nobody resets it).
+template <bool NORM, bool MAXOP, bool RAW, bool DET = false>
 __device__ __forceinline__ void op_scan_body(const OpArgs &a) {
     using Cfg = ScanCfg;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -568,7 +571,7 @@ __device__ __forceinline__ void op_scan_body(const OpArgs &a) {
         PixelSums sums = {0.0f, 0.0f, 0.0f};
         EntryRegs<Cfg> e;
         float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-        build_records<Cfg, NORM, false, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+        build_records<Cfg, NORM, false, RAW, DET>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
         T_STAMP(s, 6);
         stream_planes<Cfg, NORM, MAXOP, false, false, false, true, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
         T_STAMP(s, 59);
@@ -593,7 +596,9 @@ __device__ __forceinline__ void op_scan_body(const OpArgs &a) {
         const uint32_t tasks = room ? (all + (uint32_t)Cfg::SEG - 1u) / (uint32_t)Cfg::SEG : ntask;
         const uint32_t want = min(a.sink_t, max(tasks, 1u));
         const uint32_t base = want ? atomicAdd(f.totals + 6, want) : a.sink_cap;
-        hd[11] = (want && base <= a.sink_cap && want <= a.sink_cap - base) ? base : 0xffffffffu;
+        const bool slabs = want && base <= a.sink_cap && want <= a.sink_cap - base;
+        hd[11] = slabs ? base : 0xffffffffu;
+        if constexpr (DET) { if (!room || !slabs) atomicAdd(f.totals + DET_FALLBACK_WORD, 1u); }
         L.misc[10] = room ? off : 0xffffffffu;
     }
     __syncthreads();
@@ -623,7 +628,7 @@ constexpr uint32_t SINK_P = SLR_SINK_PIECES, SINK_T = SLR_SINK_TASKS, SINK_MINE 
 #define SINK_STAMP(slot, v) do { } while (0)
 #endif
 static_assert(SINK_T <= 16, "slab bits of the arrival word");
-template <bool NORM, bool MAXOP, bool RAW>
+template <bool NORM, bool MAXOP, bool RAW, bool DET = false>
 __device__ __forceinline__ void op_sink_body(const OpArgs &a) {
     using Cfg = ScanCfg;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -785,7 +790,7 @@ __device__ __forceinline__ void op_sink_body(const OpArgs &a) {
                 EntryRegs<Cfg> e;
                 float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
                 SINK_STAMP(5, wall_clock64());
-                build_records<Cfg, NORM, false, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+                build_records<Cfg, NORM, false, RAW, DET>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB, DET && listed);
                 SINK_STAMP(6, wall_clock64());
                 stream_planes<Cfg, NORM, MAXOP, false, true, true, true, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, !wrote, false, slab);
                 SINK_STAMP(7, wall_clock64());
@@ -880,6 +885,11 @@ template <bool PASSES>
 __global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_blend_kernel(OpArgs a) { op_rows_body<true, false, PASSES, true>(a); }
 __global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_blend_kernel(OpArgs a) { op_scan_body<true, false, true>(a); }
 __global__ __launch_bounds__(TT, 4) void op_sink_blend_kernel(OpArgs a) { op_sink_body<true, false, true>(a); }
+// ... and the RAW forms with canonical record lists (DET): the deterministic forward of the training step's blend
+template <bool PASSES>
+__global__ __launch_bounds__(TT, PASSES ? 1 : SLR_WAVES_ROWS) void op_rows_blend_det_kernel(OpArgs a) { op_rows_body<true, false, PASSES, true, true>(a); }
+__global__ __launch_bounds__(TT, SLR_WAVES_SCAN) void op_scan_blend_det_kernel(OpArgs a) { op_scan_body<true, false, true, true>(a); }
+__global__ __launch_bounds__(TT, SLR_WAVES_SINK_DET) void op_sink_blend_det_kernel(OpArgs a) { op_sink_body<true, false, true, true>(a); }
 
 // =========================================================================== small kernels
 
@@ -1010,11 +1020,12 @@ static int do_rowbin(const float *flow, OpWs &w, int N, int H, int W, bool clean
     return 0;
 }
 
-template <bool NORM, bool MAXOP, bool RAW>
+template <bool NORM, bool MAXOP, bool RAW, bool DET>
 static int launch_rows(OpArgs &a, OpWs &w, hipStream_t st) {
+    static_assert(!DET || RAW, "the deterministic kernels exist in the RAW form");
     static LdsOptIn attr_main, attr_pass;
-    void (*const k_main)(OpArgs) = RAW ? op_rows_blend_kernel<false> : op_rows_kernel<NORM, MAXOP, false>;
-    void (*const k_pass)(OpArgs) = RAW ? op_rows_blend_kernel<true> : op_rows_kernel<NORM, MAXOP, true>;
+    void (*const k_main)(OpArgs) = DET ? op_rows_blend_det_kernel<false> : RAW ? op_rows_blend_kernel<false> : op_rows_kernel<NORM, MAXOP, false>;
+    void (*const k_pass)(OpArgs) = DET ? op_rows_blend_det_kernel<true> : RAW ? op_rows_blend_kernel<true> : op_rows_kernel<NORM, MAXOP, true>;
     if (int e = lds_opt_in((const void *)k_main, 159 * 1024, attr_main)) return e;
     if (int e = lds_opt_in((const void *)k_pass, 159 * 1024, attr_pass)) return e;
     a.f.rowlist[0] = w.rowlist; a.f.items = w.items; a.f.totals = w.totals; a.f.defer = w.defer; a.f.items_cap = w.L.items_cap;
@@ -1033,11 +1044,12 @@ static int launch_rows(OpArgs &a, OpWs &w, hipStream_t st) {
     return 0;
 }
 
-template <bool NORM, bool MAXOP, bool RAW>
+template <bool NORM, bool MAXOP, bool RAW, bool DET>
 static int launch_scan(OpArgs &a, OpWs &w, hipStream_t st) {
+    static_assert(!DET || RAW, "the deterministic kernels exist in the RAW form");
     static LdsOptIn attr, attr_s;
-    void (*const k_scan)(OpArgs) = RAW ? op_scan_blend_kernel : op_scan_kernel<NORM, MAXOP>;
-    void (*const k_sink)(OpArgs) = RAW ? op_sink_blend_kernel : op_sink_kernel<NORM, MAXOP>;
+    void (*const k_scan)(OpArgs) = DET ? op_scan_blend_det_kernel : RAW ? op_scan_blend_kernel : op_scan_kernel<NORM, MAXOP>;
+    void (*const k_sink)(OpArgs) = DET ? op_sink_blend_det_kernel : RAW ? op_sink_blend_kernel : op_sink_kernel<NORM, MAXOP>;
     if (int e = lds_opt_in((const void *)k_scan, 159 * 1024, attr)) return e;
     if (int e = lds_opt_in((const void *)k_sink, (int)ScanCfg::LDS_BYTES, attr_s)) return e;
     a.f.box = (const SrcBox *)w.box; a.f.totals = w.totals; a.f.defer = w.defer;
@@ -1073,7 +1085,7 @@ static int launch_scan(OpArgs &a, OpWs &w, hipStream_t st) {
 
 // One call of the operator: front end by grid size / flags, then the tile kernel(s) -- once per plane group (plane_group: one group unless
 // the sample's plane stack reaches 2 GiB).
-template <bool NORM, bool MAXOP, bool RAW = false>
+template <bool NORM, bool MAXOP, bool RAW = false, bool DET = false>
 static int do_op(OpArgs &a, int ws_flags, void *ws, size_t ws_bytes, hipStream_t st, const char *who) {
     OpWs w;
     if (int e = op_ws_open(w, a.s.N, a.s.H, a.s.W, ws, ws_bytes, who)) return e;
@@ -1093,7 +1105,7 @@ static int do_op(OpArgs &a, int ws_flags, void *ws, size_t ws_bytes, hipStream_t
     for (int pb = 0; pb < C; pb += gp) {
         a.s.in = in + (size_t)pb * hw; a.f.out = out + (size_t)pb * hw;
         a.s.C = C - pb < gp ? C - pb : gp;
-        if (int e = fe == 1 ? launch_scan<NORM, MAXOP, RAW>(a, w, st) : launch_rows<NORM, MAXOP, RAW>(a, w, st)) return e;
+        if (int e = fe == 1 ? launch_scan<NORM, MAXOP, RAW, DET>(a, w, st) : launch_rows<NORM, MAXOP, RAW, DET>(a, w, st)) return e;
     }
     return 0;
 }
@@ -1101,16 +1113,18 @@ static int do_op(OpArgs &a, int ws_flags, void *ws, size_t ws_bytes, hipStream_t
 // One direction of the training step's blend (blend.hip): sum[n,c] = splat(values w), norm[n] = splat(w) with
 // w = exp(clamp(logits - zmax[0], lo, hi)) * (second ? 1 - alpha[n] : alpha[n]) applied where the softmax mode applies exp(metric) --
 // the RAW instantiations of the tile kernels: raw sums, the raw normaliser plane, every element of both written.
+// det: their DET forms -- sum and norm are then a function of the inputs, the shape and the front-end settings alone, as long as the
+// workspace's fallback word stays 0 (slr_splat_fallback_count_offset).
 int splat_weighted_sum(const float *values, const float *logits, const float *zmax, const float *alpha, int second, float lo, float hi,
                        const float *flow, float *sum, float *norm, int N, int C, int H, int W, void *ws, size_t ws_bytes, int ws_flags,
-                       hipStream_t st) {
+                       bool det, hipStream_t st) {
     if (int e = op_check_dims(N, C, H, W, __func__)) return e;
     OpArgs a = {};
     a.s.in = values; a.s.mul = logits; a.s.mulmax = zmax; a.f.flow[0] = flow; a.f.out = sum; a.f.norm_out = norm;
     a.s.N = N; a.s.C = C; a.s.H = H; a.s.W = W;
     a.s.mulmode = !logits ? MUL_ONE : zmax ? MUL_EXP_SHIFT : MUL_EXP;
     a.s.alpha = alpha; a.s.second = second; a.s.clamp_lo = lo; a.s.clamp_hi = hi;
-    return do_op<true, false, true>(a, ws_flags, ws, ws_bytes, st, __func__);
+    return det ? do_op<true, false, true, true>(a, ws_flags, ws, ws_bytes, st, __func__) : do_op<true, false, true>(a, ws_flags, ws, ws_bytes, st, __func__);
 }
 
 }  // namespace slr
@@ -1144,6 +1158,11 @@ SLR_EXPORT void slr_splat_set_scan_shape(int pieces, int groups, int defer_wg, i
 SLR_EXPORT size_t slr_splat_workspace_bytes(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
     return op_layout(N, H, W).total;
+}
+
+SLR_EXPORT size_t slr_splat_fallback_count_offset(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return op_layout(N, H, W).off_totals + (size_t)DET_FALLBACK_WORD * 4;
 }
 
 SLR_EXPORT int slr_splat_workspace_init(void *ws, size_t ws_bytes, int N, int H, int W, void *stream) {

@@ -222,7 +222,9 @@ __device__ __forceinline__ rsrc_t sample_planes(const TileShared &s, const Piece
 
 // A piece in ONE pass (the main kernels: no loop over work): lists -> entries -> records -> planes [cb, ce).  Returns false, with
 // nothing written, when the piece turns out to hold more than SEG entries (the pass-by-pass launch takes it).
-template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false>
+// DET: the record lists in canonical order (build_records); the MODE 1 walk's entry slots may stay as the waves took them -- the rank
+// goes by the entries' source words, not by their slots.
+template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false, bool DET = false>
 __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileFrame &f, const TileLds<Cfg> &L, const Piece &p, int tid,
                                                 const TileScalars &k, int cb, int ce) {
     T_STAMP(s, 0);
@@ -231,9 +233,11 @@ __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileF
     rows_setup<Cfg, SORTED>(f, L, p, tid);
     T_STAMP(s, 1);
     uint32_t total;
+    bool canon = false;                                    // DET: the entry slots are reproducible (the sorted list's first slots)
     if (p.whole && !p.ovf0 && !p.ovf1 && p.cnt0 + p.cnt1 <= (uint32_t)Cfg::SEG) {
         rows_walk<Cfg, 0, true, G2>(s, f, L, p, tid, 0u, 0u, (uint32_t)Cfg::SEG);
         total = p.cnt0 + p.cnt1;                           // exact (the binning kernel), <= SEG (the plan)
+        canon = true;
         __syncthreads();
     } else {
         rows_walk<Cfg, 1, true, G2>(s, f, L, p, tid, 0u, 0u, (uint32_t)Cfg::SEG);
@@ -246,7 +250,7 @@ __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileF
     const rsrc_t rin = sample_planes(s, p, k.hw4);
     EntryRegs<Cfg> e;
     float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-    build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB);
+    build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW, DET>(s, L, p, tid, total, rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1, e, preA, preB, DET && canon);
     T_STAMP(s, 6);
     PixelSums sums = {0.0f, 0.0f, 0.0f};
     stream_planes<Cfg, NORM, MAXOP, G2, false, false, false, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, true, true);
@@ -257,7 +261,7 @@ __device__ __forceinline__ bool rows_piece_once(const TileShared &s, const TileF
 // A piece pass by pass (more than SEG entries: an octant that is a sink by itself; any pathological flow): a count pass gives every
 // wave its first ordinal, pass si stages the entries with ordinals [si * SEG, (si + 1) * SEG); every work-item accumulates its output
 // pixel through its own earlier stores and normalises in the last pass.
-template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false>
+template <class Cfg, bool SORTED, bool NORM, bool MAXOP, bool G2, bool RAW = false, bool DET = false>
 __device__ __forceinline__ void rows_piece_passes(const TileShared &s, const TileFrame &f, const TileLds<Cfg> &L, const Piece &p, int tid,
                                                   const TileScalars &k, int cb, int ce) {
     rows_setup<Cfg, SORTED>(f, L, p, tid);
@@ -275,8 +279,8 @@ __device__ __forceinline__ void rows_piece_passes(const TileShared &s, const Til
         __syncthreads();
         EntryRegs<Cfg> e;
         float preA[Cfg::EPT][4], preB[Cfg::EPT][4];
-        build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW>(s, L, p, tid, min((uint32_t)Cfg::SEG, all - lo), rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1,
-                                                         e, preA, preB);
+        build_records<Cfg, NORM || (Cfg::NDIR > 1), G2, RAW, DET>(s, L, p, tid, min((uint32_t)Cfg::SEG, all - lo), rin, k.hw4, cb, ce - 1, k.shift, k.sc0, k.sc1,
+                                                         e, preA, preB, DET);      // (MODE 2: reproducible ordinals)
         stream_planes<Cfg, NORM, MAXOP, G2, true, false, false, RAW>(s, f, L, p, tid, rin, k.hw4, cb, ce, e, preA, preB, sums, si == 0, si + 1 == npass);
     }
     __syncthreads();

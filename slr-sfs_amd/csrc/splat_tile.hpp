@@ -192,10 +192,20 @@ __device__ __forceinline__ void prefetch_planes(rsrc_t rin, const EntryRegs<Cfg>
 // pure bilinear weights).  G2 (a second weight group shares the records): the records keep the PURE bilinear weights, m multiplies
 // the first group's values when they are staged, and the entry's slot of a special chunk carries  m | in2 * m2 | m2.
 // RAW (with WEIGHTED): the blend weight of TileShared.alpha / clamp_lo / clamp_hi / second instead of mulmode's.
-template <class Cfg, bool WEIGHTED, bool G2, bool RAW = false>
+// DET (the deterministic blend forward): a record's place in its pixel's list is its RANK by the entry's source word (source pixel |
+// direction << 31: unique within a piece), not the slot the LDS atomic of 1a returned -- which depends on the order in which the
+// workgroup's eight waves got to that counter, and with it the order of every sum the gather forms.  1c only parks the staged-entry
+// offsets in arrival order; after a barrier every work-item counts, for each of its <= 4 * EPT records, the records of the same list whose
+// entry carries a smaller source word (two LDS reads per comparison: the parked offset, then that entry's first word in the entry
+// array, which is alive until the first chunk is staged) and writes the record at list start + rank.  A list of n records costs n
+// comparisons per record, paid by the n work-items that own its records (an entry gives a pixel at most one record): no lane ever pays
+// n * n, the sum over a tile is sum n^2 / 512 per work-item.  The list LENGTHS still come from the atomics (integer counts: exact).
+// canon (uniform): the entries already sit at reproducible slots (MODE 0 / MODE 2 walks, the listed tasks of the sink launch) -- the
+// parked offset IS a canonical key then, one LDS read per comparison.
+template <class Cfg, bool WEIGHTED, bool G2, bool RAW = false, bool DET = false>
 __device__ __forceinline__ void build_records(const TileShared &s, const TileLds<Cfg> &L, const Piece &p, int tid, uint32_t total,
                                               rsrc_t rin, uint32_t hw4, int c0, int cmax, float shift, float sc0, float sc1,
-                                              EntryRegs<Cfg> &e, float (&preA)[Cfg::EPT][4], float (&preB)[Cfg::EPT][4]) {
+                                              EntryRegs<Cfg> &e, float (&preA)[Cfg::EPT][4], float (&preB)[Cfg::EPT][4], bool canon = false) {
     constexpr int EPT = Cfg::EPT;
     uint32_t dir[EPT];
     float X[EPT], Y[EPT], mm[EPT], l2[EPT], v2[EPT];
@@ -270,11 +280,48 @@ __device__ __forceinline__ void build_records(const TileShared &s, const TileLds
         L.off[tid] = (uint16_t)ex;
     }
     __syncthreads();
+    if constexpr (DET) {
+        static_assert(Cfg::REC6 && !G2, "the parked offsets are the 16-bit entry words of 6-byte records; the entry array must still hold the entries");
 #pragma unroll
-    for (int j = 0; j < EPT; ++j)                     // 1c
+        for (int j = 0; j < EPT; ++j)                 // 1c: the entry offsets, in arrival order
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (ts[j][k] != 0xffffffffu) L.rec_put(L.off[ts[j][k] >> 16] + (ts[j][k] & 0xffffu), (uint32_t)tid + (uint32_t)j * TT, w[j][k]);
+            for (int k = 0; k < 4; ++k)
+                if (ts[j][k] != 0xffffffffu) L.rec_e[L.off[ts[j][k] >> 16] + (ts[j][k] & 0xffffu)] = (uint16_t)(((uint32_t)tid + (uint32_t)j * TT) * 16u);
+        __syncthreads();
+        const char *ent = reinterpret_cast<const char *>(L.ent4);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {               // 1d: rank by source word
+            const uint32_t key = (e.off[j] >> 2) | (dir[j] << 31);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (ts[j][k] == 0xffffffffu) continue;
+                const uint32_t px = ts[j][k] >> 16, first = L.off[px], n = L.cnt[px];
+                uint32_t rank = 0;
+                if (canon) {                          // (uniform)
+                    const uint32_t own = ((uint32_t)tid + (uint32_t)j * TT) * 16u;
+#pragma unroll 4
+                    for (uint32_t i = 0; i < n; ++i) rank += (uint32_t)L.rec_e[first + i] < own ? 1u : 0u;
+                } else {
+#pragma unroll 4
+                    for (uint32_t i = 0; i < n; ++i)
+                        rank += *reinterpret_cast<const uint32_t *>(ent + L.rec_e[first + i]) < key ? 1u : 0u;
+                }
+                ts[j][k] = first + rank;
+            }
+        }
+        __syncthreads();                              // (every parked offset has been read)
+#pragma unroll
+        for (int j = 0; j < EPT; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ts[j][k] != 0xffffffffu) L.rec_put(ts[j][k], (uint32_t)tid + (uint32_t)j * TT, w[j][k]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j)                 // 1c
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ts[j][k] != 0xffffffffu) L.rec_put(L.off[ts[j][k] >> 16] + (ts[j][k] & 0xffffu), (uint32_t)tid + (uint32_t)j * TT, w[j][k]);
+    }
     if (tid == 0) { L.val4[Cfg::NULL_E] = make_float4(0.f, 0.f, 0.f, 0.f); L.rec_put(Cfg::NULLREC, Cfg::NULL_E, 0.0f); }
     __syncthreads();
 }

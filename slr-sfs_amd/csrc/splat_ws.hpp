@@ -14,7 +14,7 @@ struct OpLayout {
     size_t off_rowinfo;   // uint64[nt][2]  what the rowcnt words held when the plan was made (the plan leaves rowcnt zero for the next binning)
     size_t off_rowlist;   // RowRec[nt][ROW_CAP]  the tile's row segments as rowbin_kernel appended them
     size_t off_items;     // ItemDesc[items_cap]
-    size_t off_totals;    // uint32[16]  [0] items, [4] deferred pieces, [5] heavy items, [6] arrivals of the deferred launch; [8..15]: the same for slr_synth_group's plan
+    size_t off_totals;    // uint32[64]  [0] items, [4] deferred pieces, [5] heavy items, [6] arrivals of the deferred launch; [8..15]: the same for slr_synth_group's plan; [16..23] the sink launch's draw counters; [DET_FALLBACK_WORD] capacity fallbacks of deterministic calls (sticky: zeroed with the workspace, only ever incremented)
     size_t off_defer;     // uint32[items_cap]  pieces of more than a segment (appended by their workgroups)
     size_t off_box;       // SrcBox[nt]  scan front end: destination box of every source tile
     size_t off_ctl;       // uint32[64]  arrival counter (second level) of rowbin_kernel
@@ -29,6 +29,8 @@ struct OpLayout {
     size_t off_defer2;    // uint32[items2_cap]
     size_t total;
 };
+
+constexpr uint32_t DET_FALLBACK_WORD = 32;     // word of totals[] (256 bytes) that no kernel resets
 
 inline OpLayout op_layout(int N, int H, int W) {
     OpLayout L;

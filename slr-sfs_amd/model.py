@@ -92,15 +92,16 @@ class TrainingModel(nn.Module):
     detached: for reporting), GTMotion.
 
     ``vgg``: the ``VGG19Features`` of the content loss.  encoder_widths / decoder_widths / decoder_updown: other widths than the
-    reference's (tests)."""
+    reference's (tests).  ``deterministic`` (keyword only, a bool): the run-to-run reproducible forward of ``splat_blend`` -- with it two
+    iterations from the same state are bit-equal (``training.splat_blend_fallback_count`` must read 0: DESIGN 3.7.1)."""
 
-    def __init__(self, opts, vgg=None, *, encoder_widths=None, decoder_widths=None, decoder_updown=None):
+    def __init__(self, opts, vgg=None, *, encoder_widths=None, decoder_widths=None, decoder_updown=None, deterministic=False):
         super().__init__()
         check_options(opts)
         self.opt = opts
         feat = int(_value(opts, "out_channel", _value(opts, "ngf", 64)))
         self.encoder = TrainableEncoderWithZ(cin=3, feat=feat, widths=encoder_widths, spectral=True)
-        self.synthesis = TrainingSynthesis(opts)
+        self.synthesis = TrainingSynthesis(opts, deterministic=deterministic)
         self.projector = TrainableDecoderPconv2(cin=int(_value(opts, "ngf", feat)), cout=3, widths=decoder_widths, updown=decoder_updown,
                                                 spectral=True)
         if self.projector.blocks[0].conv_aa.cin != feat:

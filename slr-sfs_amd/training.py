@@ -10,7 +10,7 @@ import math
 
 import torch
 
-from ._lib import WS_CLEAN, call, lib, require_device, workspace
+from ._lib import BLEND_DETERMINISTIC, WS_CLEAN, call, lib, require_device, workspace
 from .euler_integration_manipulator import EulerIntegration
 
 _UNSUPPORTED = ("use_softmax_splatter_v2", "use_softmax_splatter_v3", "use_3d_splatter", "use_mesh_splatter", "random_ff_mask")
@@ -55,11 +55,11 @@ def _global_max(z):
 
 
 class _SplatBlend(torch.autograd.Function):
-    """forward(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, lo, hi, subtract_max, eps); saved: the inputs, the two maxima,
-    the output and one normaliser plane per sample."""
+    """forward(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, lo, hi, subtract_max, eps[, deterministic]); saved: the inputs,
+    the two maxima, the output and one normaliser plane per sample."""
 
     @staticmethod
-    def forward(ctx, start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, lo, hi, subtract_max, eps):
+    def forward(ctx, start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, lo, hi, subtract_max, eps, deterministic=False):
         N, C, H, W = start_fs.shape
         dev = start_fs.device
         zmax_f = _global_max(z_start) if subtract_max and z_start is not None else None
@@ -68,8 +68,8 @@ class _SplatBlend(torch.autograd.Function):
         nbytes = int(lib().slr_splat_blend_ws_bytes(N, C, H, W))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         ws = workspace(start_fs, "a", N, C, H, W)
-        call("slr_splat_blend_forward", dev, start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, zmax_f, zmax_p, lo, hi, eps,
-             out, norm, N, C, H, W, ws, ws.numel(), WS_CLEAN, scratch, nbytes)
+        call("slr_splat_blend_forward_ex", dev, start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, zmax_f, zmax_p, lo, hi, eps,
+             out, norm, N, C, H, W, ws, ws.numel(), WS_CLEAN, BLEND_DETERMINISTIC if deterministic else 0, scratch, nbytes)
         ctx.save_for_backward(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, zmax_f, zmax_p, out, norm)
         ctx.consts = (lo, hi, eps)
         ctx.mark_non_differentiable(norm)
@@ -90,11 +90,11 @@ class _SplatBlend(torch.autograd.Function):
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=start_fs.device)
             call("slr_splat_blend_backward", start_fs.device, start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, zmax_f, zmax_p,
                  lo, hi, eps, out, norm, grad_out, *grads, N, C, H, W, scratch, nbytes)
-        return (*grads, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None)
 
 
 def splat_blend(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, clamp_z=(-20.0, 20.0), subtract_max=True, eps=1e-8,
-                return_norm=False):
+                return_norm=False, deterministic=False):
     """out = (splat(start_fs w_f, flow_f) + splat(end_fs w_p, flow_p)) / max(splat(w_f, flow_f) + splat(w_p, flow_p), eps), [N,C,H,W], with
     w_f = exp(clamp(z_start - z_start.max())) * alpha, w_p = exp(clamp(z_end - z_end.max())) * (1 - alpha) -- the reference's
     animating_softmax_splating.py:587-692, differentiable in all six tensors (``needs_input_grad`` is honoured: a gradient nobody
@@ -104,12 +104,17 @@ def splat_blend(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, clamp_z
     [N,2,H,W], alpha: N values on the device (any shape; not differentiated).  clamp_z: (lo, hi) or None (``no_clamp_Z``);
     subtract_max=False: ``use_softmax_splatter_v1``.  The same tensor may serve both directions: autograd adds its two gradients.
     return_norm: also the normaliser plane [N,1,H,W] (no gradient).
+    deterministic (a bool; anything else raises TypeError): the forward's deterministic tile kernels -- out and the normaliser are the same
+    bits from run to run, whatever else the device is doing, while ``splat_blend_fallback_count`` reads 0.  The backward has
+    that property already, given the forward's result.  torch's global deterministic-algorithms switch is not consulted.
 
     d/dz: zero where the clamp bites, and the maximum's element also receives minus the sum of the others'.  Where several elements
     hold the maximum, the first one in memory receives all of it -- torch splits it evenly among them; for a learnt logit plane a tie is
     a rounding accident.  A source pixel whose target coordinate is not representable (non-finite flow, |x + flow| >= 2^30) contributes
     nothing and its gradients are exactly 0.  CPU tensors raise NotImplementedError; wrong dtype, shape or layout raise before the device
     is touched."""
+    if not isinstance(deterministic, bool):
+        raise TypeError(f"slr_sfs_amd.splat_blend: deterministic must be a bool, got {type(deterministic).__name__}")
     _check_inputs(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha)
     lo, hi = (-math.inf, math.inf) if clamp_z is None else (float(clamp_z[0]), float(clamp_z[1]))
     if not lo <= hi:
@@ -117,8 +122,19 @@ def splat_blend(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha, clamp_z
     if not float(eps) > 0.0:
         raise ValueError(f"splat_blend: eps must be positive, got {eps!r}")
     out, norm = _SplatBlend.apply(start_fs, z_start, flow_f, end_fs, z_end, flow_p, alpha.detach().reshape(-1), lo, hi,
-                                  bool(subtract_max), float(eps))
+                                  bool(subtract_max), float(eps), deterministic)
     return (out, norm) if return_norm else out
+
+
+def splat_blend_fallback_count(features):
+    """The capacity fallbacks that deterministic ``splat_blend`` calls on tensors of this shape, device and stream have taken so far:
+    a one-element int32 DEVICE tensor -- a view of the cached splat workspace's sticky word (slr_splat_fallback_count_offset), read
+    without a synchronisation; zero when the workspace is made, never reset.  The run-to-run guarantee holds while it is 0."""
+    require_device(features)
+    N, C, H, W = features.shape
+    ws = workspace(features, "a", N, C, H, W)
+    off = int(lib().slr_splat_fallback_count_offset(N, H, W))
+    return ws[off:off + 4].view(torch.int32)
 
 
 def _flag(opts, name):
@@ -151,11 +167,14 @@ class TrainingSynthesis(torch.nn.Module):
     """The reference's forward() from the Euler integration to the normalised features (animating_softmax_splating.py:577-692):
     forward(start_fs, Z_f, end_fs, Z_p, motion, start_index, middle_index, end_index) -> [B,C,H,W], differentiable in the features, the
     logits and the motion field, without a host synchronisation when the indices are device tensors.  With ``train_Z`` off Z_f / Z_p are
-    ignored (the reference replaces them by ones, whose weights cancel)."""
+    ignored (the reference replaces them by ones, whose weights cancel).  ``deterministic``: passed on to ``splat_blend``."""
 
-    def __init__(self, opts=None):
+    def __init__(self, opts=None, deterministic=False):
         super().__init__()
+        if not isinstance(deterministic, bool):
+            raise TypeError(f"slr_sfs_amd.TrainingSynthesis: deterministic must be a bool, got {type(deterministic).__name__}")
         self.opts = opts
+        self.deterministic = deterministic
         self.options = _blend_options(opts)
         self.euler_integration = EulerIntegration(opts)
 
@@ -171,5 +190,6 @@ class TrainingSynthesis(torch.nn.Module):
             Z_f = Z_p = None
         else:
             Z_f, Z_p = Z_f.reshape(bs, 1, *start_fs.shape[2:]), Z_p.reshape(bs, 1, *start_fs.shape[2:])       # :590 / :639
+        # (the keyword travels only when it is set: the default call is the one it always was)
         return splat_blend(start_fs, Z_f, flow_f, end_fs, Z_p, flow_p, alpha, clamp_z=self.options["clamp_z"],
-                           subtract_max=self.options["subtract_max"])
+                           subtract_max=self.options["subtract_max"], **({"deterministic": True} if self.deterministic else {}))

@@ -13,6 +13,11 @@ Shapes: [2,64,256,256] with Euler steps (30, 59) of 60 and [1,64,768,1280] with 
 too).  A device is required: there is no CPU path for a timing.
 
     python tools/blend_bench.py --out profiles/blend_train_step.json
+
+--deterministic: the same measurement of B against D = ``splat_blend(..., deterministic=True)`` (rounds B D B D ..., one traced child each;
+the default operator of the same build is the yardstick): step time and forward kernel time of D over B as they come out.
+
+    python tools/blend_bench.py --deterministic --out profiles/blend_deterministic.json
 """
 import argparse
 import csv
@@ -81,16 +86,20 @@ def step_chain(S, c, splat, mark=None):
     return gen, lv
 
 
-def step_blend(S, c, splat, mark=None):
+def step_blend(S, c, splat, mark=None, deterministic=False):
     lv = {k: c[k].detach().requires_grad_(True) for k in NAMES}
-    out = S.splat_blend(*[lv[k] for k in NAMES], c["alpha"])
+    out = S.splat_blend(*[lv[k] for k in NAMES], c["alpha"], deterministic=deterministic)
     if mark:
         mark()
     out.backward(c["go"])
     return out, lv
 
 
-STEP = {"A": step_chain, "B": step_blend}
+def step_blend_det(S, c, splat, mark=None):
+    return step_blend(S, c, splat, mark, deterministic=True)
+
+
+STEP = {"A": step_chain, "B": step_blend, "D": step_blend_det}
 
 
 def need_device():
@@ -205,6 +214,47 @@ def measure(S, args, shape_name):
     return res
 
 
+def measure_deterministic(S, args, shape_name):
+    """B (default) and D (deterministic) alternated in one process; D's cost as a ratio to B, whatever it is."""
+    shape, steps = SHAPES[shape_name]
+    c, splat = make_case(S, shape, steps), None
+    res = {"shape": list(shape), "euler_steps": list(steps), "rounds": args.rounds, "steps_per_round": args.steps}
+    (ob, lb), (od, ld) = step_blend(S, c, splat), step_blend_det(S, c, splat)
+    rel = lambda x, y: float((x - y).abs().max() / y.abs().max())
+    res["max_rel_difference_D_vs_B"] = {"out": rel(od.detach(), ob.detach()), **{k: rel(ld[k].grad, lb[k].grad) for k in NAMES}}
+    outs = [step_blend_det(S, c, splat)[0].detach() for _ in range(4)]
+    res["D_four_calls_bit_equal"] = bool(all(torch.equal(o, od.detach()) for o in outs))
+    res["D_fallback_count"] = int(S.training.splat_blend_fallback_count(c["start_fs"]).item())
+    del ob, lb, od, ld, outs
+    for v in "BD":
+        for _ in range(args.warmup):
+            STEP[v](S, c, splat)
+    torch.cuda.synchronize()
+    times = {"B": [], "D": []}
+    for _ in range(args.rounds):
+        for v in "BD":
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                STEP[v](S, c, splat)
+            e1.record()
+            e1.synchronize()
+            times[v].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+    for v in "BD":
+        t = times[v]
+        res[f"{v}_step_us_rounds"] = [round(x, 2) for x in t]
+        res[f"{v}_step_us"] = round(float(np.median(t)), 2)
+        res[f"{v}_step_us_min_max"] = [round(float(min(t)), 2), round(float(max(t)), 2)]
+    res["D_over_B_step_time"] = round(res["D_step_us"] / res["B_step_us"], 4)
+    if not args.no_trace:
+        for v in "BD":
+            res[f"{v}_trace"] = kernel_time_per_step(args, shape_name, v)
+        res["D_over_B_forward_kernel_time"] = round(res["D_trace"]["forward_kernel_us"] / res["B_trace"]["forward_kernel_us"], 4)
+    else:
+        res["forward_kernel_time"] = "not measured (--no-trace)"
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=5)
@@ -216,7 +266,8 @@ def main():
     ap.add_argument("--trace-warmup", type=int, default=3)
     ap.add_argument("--trace-dir", default=None, help="where the traces' temporary directories go")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=["A", "B"], help="(child of a trace) run this variant's steps and nothing else")
+    ap.add_argument("--deterministic", action="store_true", help="B against D = splat_blend(..., deterministic=True) instead of A against B")
+    ap.add_argument("--only", choices=["A", "B", "D"], help="(child of a trace) run this variant's steps and nothing else")
     ap.add_argument("--shape", choices=list(SHAPES), default="train_2x64x256x256")
     args = ap.parse_args()
     if not args.only:
@@ -226,9 +277,14 @@ def main():
     S._lib.lib()
     if args.only:
         return run_only(S, args)
-    doc = {"tool": "tools/blend_bench.py", "device": torch.cuda.get_device_name(0),
-           "A": "composed chain on ModuleSoftsplat('summation') + torch autograd", "B": "slr_sfs_amd.splat_blend",
-           "cases": {name: measure(S, args, name) for name in args.shapes}}
+    if args.deterministic:
+        doc = {"tool": "tools/blend_bench.py --deterministic", "device": torch.cuda.get_device_name(0),
+               "B": "slr_sfs_amd.splat_blend", "D": "slr_sfs_amd.splat_blend(..., deterministic=True)",
+               "cases": {name: measure_deterministic(S, args, name) for name in args.shapes}}
+    else:
+        doc = {"tool": "tools/blend_bench.py", "device": torch.cuda.get_device_name(0),
+               "A": "composed chain on ModuleSoftsplat('summation') + torch autograd", "B": "slr_sfs_amd.splat_blend",
+               "cases": {name: measure(S, args, name) for name in args.shapes}}
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:

@@ -15,6 +15,11 @@ kernels.  The VGG19 of the content loss has random weights (its cost does not de
 writes it too).  A device is required.
 
     python tools/train_step_bench.py --out profiles/train_step.json
+
+--deterministic: the deferred iteration of ``TrainingModel(..., deterministic=True)`` against the deferred iteration of the default model,
+alternated the same way (the default model of the same build and process is the yardstick; the ratio is reported as it comes out).
+
+    python tools/train_step_bench.py --deterministic --out profiles/train_step_deterministic.json
 """
 import argparse
 import csv
@@ -33,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = ("deferred", "per_layer")
+DET_VARIANTS = ("default", "deterministic")
 MARKER = "slr::normalize_kernel("        # a kernel of the library that an iteration does not launch: brackets the traced iterations
 PAIR = ("slr::spectral_dot_multi_kernel", "slr::spectral_grad_multi_kernel", "slr::spectral_dot_kernel", "slr::spectral_grad_kernel")
 B, W, T = 2, 256, (0, 30, 59)
@@ -44,9 +50,9 @@ def options():
                                  discriminator_losses="pix2pixHD", ndf=64, ngf=64, out_channel=64, W=W, Z_model="encoder")
 
 
-def make(S, deferred):
+def make(S, deferred, deterministic=False):
     torch.manual_seed(1234)
-    model = S.TrainingModel(options(), S.losses.VGG19Features())
+    model = S.TrainingModel(options(), S.losses.VGG19Features(), deterministic=deterministic)
     trainer = S.Trainer(model, options()).cuda().train()
     model.defer_weight_grad(deferred)
     return trainer
@@ -63,7 +69,7 @@ def batch():
 
 def run_only(S, args):
     tiny = torch.ones(1, 2, 1, 1, device="cuda")
-    trainer, b = make(S, args.only == "deferred"), batch()
+    trainer, b = make(S, args.only != "per_layer", args.only == "deterministic"), batch()
     for _ in range(args.warmup):
         trainer(iter([b]))
     torch.cuda.synchronize()
@@ -105,6 +111,46 @@ def summary(t):
     return dict(step_ms=round(float(np.median(t)), 3), step_ms_min_max=[round(min(t), 3), round(max(t), 3)], step_ms_rounds=[round(x, 3) for x in t])
 
 
+def main_deterministic(S, args):
+    doc = {"tool": "tools/train_step_bench.py --deterministic", "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+           "shape": [B, 3, W, W], "ndf": 64, "euler_steps": [T[1] - T[0], T[2] + 1 - T[1]],
+           "default": "TrainingModel(...): the default forward splat", "deterministic": "TrainingModel(..., deterministic=True)",
+           "rounds": args.rounds, "steps_per_round": args.steps,
+           "step_ms": "device events around a block of iterations, per iteration: what a training loop waits for, host launch cost included"}
+    trainers, b = {v: make(S, True, v == "deterministic") for v in DET_VARIANTS}, batch()
+    times = {v: [] for v in DET_VARIANTS}
+    for t in trainers.values():
+        for _ in range(args.warmup):
+            t(iter([b]))
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for v, t in trainers.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                t(iter([b]))
+            e1.record()
+            e1.synchronize()
+            times[v].append(e0.elapsed_time(e1) / args.steps)
+    for v in DET_VARIANTS:
+        doc[v] = dict(summary(times[v]), what=doc[v])
+    feats = torch.empty(B, 64, W, W, device="cuda")
+    doc["fallback_count"] = int(S.training.splat_blend_fallback_count(feats).item())
+    doc["deterministic_over_default"] = round(doc["deterministic"]["step_ms"] / doc["default"]["step_ms"], 4)
+    doc["difference_inside_the_spread_of_the_rounds"] = bool(max(times["default"]) >= min(times["deterministic"]) and max(times["deterministic"]) >= min(times["default"]))
+    if not args.no_trace:
+        del trainers
+        torch.cuda.empty_cache()
+        for v in DET_VARIANTS:
+            doc[v]["trace"] = trace(args, v)
+    else:
+        doc["kernel_time"] = "not measured (--no-trace)"
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+    print(json.dumps(doc, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
@@ -115,7 +161,8 @@ def main():
     ap.add_argument("--trace-warmup", type=int, default=2)
     ap.add_argument("--trace-dir", default=None, help="where the traces' temporary directories go")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=VARIANTS, help="(child of a trace) run this variant's iterations and nothing else")
+    ap.add_argument("--deterministic", action="store_true", help="the deterministic forward splat against the default one (both deferred)")
+    ap.add_argument("--only", choices=VARIANTS + DET_VARIANTS, help="(child of a trace) run this variant's iterations and nothing else")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/train_step_bench.py: no ROCm device -- a timing has no CPU path")
@@ -124,6 +171,8 @@ def main():
     S._lib.lib()
     if args.only:
         return run_only(S, args)
+    if args.deterministic:
+        return main_deterministic(S, args)
     doc = {"tool": "tools/train_step_bench.py", "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
            "shape": [B, 3, W, W], "ndf": 64, "euler_steps": [T[1] - T[0], T[2] + 1 - T[1]],
            "deferred": "slr_spectral_weight_grad_multi: one pair of launches per group run (six launches per generator backward)",
