@@ -589,7 +589,8 @@ int slr_ssim_mse(const void *img1, const void *img2, int u8, const float *mask, 
 int slr_vgg_prep(const void *img, int u8, int from01, float *out, int N, int H, int W, void *stream);
 
 /* nn.ReLU + nn.MaxPool2d(2, stride 2) of torchvision's vgg16.features (floor mode: 45 x 80 -> 22 x 40):
- * in [N,C,H,W] -> out [N,C,H/2,W/2], both channel-blocked [N,C/8,.,.,8], C % 8 == 0, 16-byte aligned. */
+ * in [N,C,H,W] -> out [N,C,H/2,W/2], both channel-blocked [N,C/8,.,.,8], C % 8 == 0, 16-byte aligned.  A window that holds a NaN
+ * gives NaN, as torch's does (the training loss runs this kernel too). */
 int slr_relu_maxpool2x2_b8(const float *in, float *out, int N, int C, int H, int W, void *stream);
 
 /* 1 - cos_sim(relu(f0), relu(f1)) of pretrained_networks.py:11-31 and :82 (normalize_tensor eps 1e-10; mean over H, W):
@@ -619,16 +620,19 @@ int slr_l1_loss_grad(const float *pred, const float *gt, float *loss, float *gra
  * with the nn.ReLU in front of it): a, b raw (pre-ReLU) features of prediction / ground truth, g_in the gradient arriving at relu(a)
  * from the layers above, all [N,C,H,W] channel-blocked, C % 8 == 0, 16-byte aligned.
  *   sum[0] = sum |relu(a) - relu(b)|                                           (needs b and ws; the caller divides by the count)
- *   g_out  = a > 0 ? g_in + sign(relu(a) - relu(b)) * (coef * gscale[0]) : 0   (g_in = NULL counts as 0)
- *   b = NULL: g_out = a > 0 ? g_in : 0, the ReLU backward of a layer that ends no slice.
- * sum or g_out may be NULL (not both).  fp32 operations in the order written: bit-equal to the same expression in torch. */
+ *   g_out  = a <= 0 ? 0 : g_in + sign(relu(a) - relu(b)) * (coef * gscale[0])  (g_in = NULL counts as 0)
+ *   b = NULL: g_out = a <= 0 ? 0 : g_in, the ReLU backward of a layer that ends no slice.
+ * sum or g_out may be NULL (not both).  fp32 operations in the order written: bit-equal to the same expression in torch.  relu is
+ * torch.relu: a NaN in a or b makes the sum NaN; sign(NaN) = 0 and the gate closes on `<= 0` only (torch's ReLU backward), so a NaN a passes
+ * g_in and g_out holds no NaN of theirs. */
 int slr_feature_l1_gate_b8(const float *a, const float *b, const float *g_in, float *sum, float *g_out, float coef,
                            const float *gscale, int N, int C, int H, int W, void *ws, size_t ws_bytes, void *stream);
 
 /* Backward of slr_relu_maxpool2x2_b8 (nn.ReLU + nn.MaxPool2d(2, 2) of torchvision's vgg19.features): x [N,C,H,W] the raw activation,
  * g [N,C,H/2,W/2] the pooled gradient, out [N,C,H,W], all channel-blocked.  g goes to the first maximum of its window in row-major
  * order (torch's choice) if that maximum is > 0; every other element, the last row / column of an odd H / W included, gets 0.
- * Every element of out is written exactly once. */
+ * A window with NaNs: torch's max_pool2d replaces on `>` or on a NaN, so g goes to the window's LAST NaN, and torch's ReLU backward
+ * closes on `<= 0` only, so it arrives there.  Every element of out is written exactly once. */
 int slr_relu_maxpool2x2_backward_b8(const float *x, const float *g, float *out, int N, int C, int H, int W, void *stream);
 
 /* ------------------------------------------------------------------ trainable 3x3 convolutions (ABI 15; csrc/conv_grad.hip)
@@ -683,12 +687,13 @@ int slr_bn_batch_stats(const float *x, const float *mask, float eps, float *mean
 int slr_bn_train_tables(const float *mean, const float *var, const float *gain, const float *bias, float eps,
                         float *scale, float *shift, int N, int C, void *stream);
 
-/* a = relu(x * scale[n,c] - shift[n,c]) * mask (blocks.py:225-231 with partialconv2d.py:69), bit-equal to that fp32 expression;
- * mask [N,1,H,W] or NULL (no mask).  slr_bn_relu_mask is the per-channel-table form of the inference path. */
+/* a = relu(x * scale[n,c] - shift[n,c]) * mask (blocks.py:225-231 with partialconv2d.py:69), bit-equal to that fp32 expression,
+ * torch.relu's NaN included (a NaN pre-activation gives NaN, not 0); mask [N,1,H,W] or NULL (no mask).  slr_bn_relu_mask is the per-channel-table form of the inference path. */
 int slr_bn_relu_mask_train(const float *x, const float *scale, const float *shift, const float *mask, float *a,
                            int N, int C, int H, int W, int b8, void *stream);
 
-/* Backward of the two calls above for the gradient ga at a.  gy = ga * mask * [x * scale - shift > 0] (the gate is recomputed from x);
+/* Backward of the two calls above for the gradient ga at a.  gy = ga * mask * [not x * scale - shift <= 0] (the gate is recomputed from x and closes
+ * on `<= 0` only, as torch's ReLU backward: a NaN pre-activation passes the gradient on);
  * s0[n,c] = sum gy, s1[n,c] = sum gy * x;  dbias = s0, dgain = rs (s1 - m s0) with rs = (var + eps)^-1/2, both [N,C];
  * dx = gy * scale + A + B (x - m) + addend, A = -rs P / count, B = -rs^3 (Q - m P) / count, P = sum_n gain s0, Q = sum_n gain s1
  * (the gradient through mean and var = m2 - m^2 of slr_bn_batch_stats).  stored = 1: mean / var are stored statistics, A = B = 0 and
@@ -736,12 +741,13 @@ int slr_bn_nonzero_stats(const float *x, float eps, float *mean, float *var, flo
  * conv2d(mask, ones) = box3x3(msum)).  Exact integers in fp32; msum is plain in either layout of x. */
 int slr_nonzero_count_plane(const float *x, float *msum, int N, int C, int H, int W, int b8, void *stream);
 
-/* a = relu(x * scale[n,c] - shift[n,c]) * [x != 0] (models/layers/blocks.py:225-231 with partialconv2d.py:69), bit-equal to that fp32
+/* a = relu(x * scale[n,c] - shift[n,c]) * [x != 0] (models/layers/blocks.py:225-231 with partialconv2d.py:69; torch.relu: NaN stays NaN), bit-equal to that fp32
  * expression; scale, shift [N,C] from slr_bn_train_tables. */
 int slr_bn_relu_nonzero_train(const float *x, const float *scale, const float *shift, float *a,
                               int N, int C, int H, int W, int b8, void *stream);
 
-/* Backward of the calls above: slr_bn_relu_mask_backward with gy = ga * [x != 0] * [x * scale - shift > 0] and the per-channel
+/* Backward of the calls above: slr_bn_relu_mask_backward with gy = ga * [x != 0] * [not x * scale - shift <= 0] (torch's ReLU backward: a
+ * NaN pre-activation leaves the gate open) and the per-channel
  * count [C] of slr_bn_nonzero_stats.  The term A + B (x - m) of dx reaches the zero elements too, as the reference's autograd gives it.
  * NULL outputs, `stored`, addend, gain and ws as there (ws: slr_bn_nonzero_ws_bytes). */
 int slr_bn_relu_nonzero_backward(const float *x, const float *ga, const float *scale, const float *shift,

@@ -111,14 +111,15 @@ __global__ __launch_bounds__(BG_THREADS) void bn_train_forward_kernel(const floa
     bg_mask<B8>(it, mask, m);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const float r = fmaxf(e[k] * sc[k] - sh[k], 0.0f);
+        const float r = relu_nan(e[k] * sc[k] - sh[k]);  // (a NaN pre-activation stays one, as torch.relu's)
         e[k] = mask ? r * m[k] : r;
     }
     bg_store<B8>(it, a, e);
 }
 
 // ------------------------------------------------------------------ 3. its backward
-// gy = ga * mask * [x * scale - shift > 0] at the thread's elements (the forward's own fp32 expression decides the gate)
+// gy = ga * mask * [not x * scale - shift <= 0] at the thread's elements (the forward's own fp32 expression decides the gate; a NaN
+// pre-activation leaves it open, as torch's ReLU backward does)
 template <bool B8>
 __device__ __forceinline__ void bg_gate(const BgItem<B8> &it, const float *__restrict__ ga, const float *__restrict__ mask,
                                         const float *__restrict__ scale, const float *__restrict__ shift, int C,
@@ -133,7 +134,7 @@ __device__ __forceinline__ void bg_gate(const BgItem<B8> &it, const float *__res
     for (int k = 0; k < K; ++k) {
         const float y = e[k] * sc[k] - sh[k];
         const float gm = mask ? g[k] * m[k] : g[k];
-        gy[k] = y > 0.0f ? gm : 0.0f;
+        gy[k] = y <= 0.0f ? 0.0f : gm;                   // torch's ReLU backward closes on `<= 0` only: a NaN pre-activation passes gm
     }
 }
 
@@ -478,12 +479,10 @@ __global__ __launch_bounds__(256) void upsample2x_backward_kernel(const float *_
         wa[b] = up_weight(2 * x0 - 1 + b, x0, W);
         wb[b] = second ? up_weight(2 * x0 + 1 + b, x0 + 1, W) : 0.0f;
     }
-    float r0 = 0.0f, r1 = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int oy = 2 * y - 1 + a;
-        const float wy = up_weight(oy, y, H);
-        const float *row = gp + (size_t)min(max(oy, 0), OH - 1) * OW;
+    // t0, t1 = the column sums of one output row for the two pixels.  torch's forward gives output 0 the taps (1, 0) on inputs 0 and 1 --
+    // l1 = 0 at the clamped source position -- so its backward sends 0 x g[0] to input 1: nothing for a finite g, a NaN for a NaN (or
+    // an infinite) one.  The term is kept as a select, which leaves the bits of every finite result alone.
+    auto row_sums = [&](const float *row, float &t0, float &t1) {
         float v[6];
         const int xl = 2 * x0 - 1, xr = 2 * x0 + 4;
         v[0] = row[xl >= 0 ? xl : 0];
@@ -495,10 +494,27 @@ __global__ __launch_bounds__(256) void upsample2x_backward_kernel(const float *_
             for (int k = 1; k < 5; ++k) v[k] = row[min(xl + k, OW - 1)];
         }
         v[5] = row[xr < OW ? xr : OW - 1];               // (a clamped address only ever meets weight 0)
-        const float t0 = ((wa[0] * v[0] + wa[1] * v[1]) + wa[2] * v[2]) + wa[3] * v[3];
-        const float t1 = ((wb[0] * v[2] + wb[1] * v[3]) + wb[2] * v[4]) + wb[3] * v[5];
+        t0 = ((wa[0] * v[0] + wa[1] * v[1]) + wa[2] * v[2]) + wa[3] * v[3];
+        t1 = ((wb[0] * v[2] + wb[1] * v[3]) + wb[2] * v[4]) + wb[3] * v[5];
+        const float z = 0.0f * v[1];                     // output column 0 onto input column 1
+        if (x0 == 0 && z != z) t1 = z;
+    };
+    float r0 = 0.0f, r1 = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int oy = 2 * y - 1 + a;
+        const float wy = up_weight(oy, y, H);
+        float t0, t1;
+        row_sums(gp + (size_t)min(max(oy, 0), OH - 1) * OW, t0, t1);
         r0 += wy * t0;
         r1 += wy * t1;
+    }
+    if (y == 1) {                                        // output row 0 onto input row 1, the same zero-weight term
+        float t0, t1;
+        row_sums(gp, t0, t1);
+        const float z0 = 0.0f * t0, z1 = 0.0f * t1;
+        if (z0 != z0) r0 = z0;
+        if (z1 != z1) r1 = z1;
     }
     float *op = gin + (plane * H + y) * (size_t)W + x0;
     op[0] = r0;
@@ -515,19 +531,41 @@ __global__ __launch_bounds__(256) void upsample2x_backward_b8_kernel(const float
     float wx[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) wx[b] = up_weight(2 * x - 1 + b, x, W);
+    // (the zero-weight terms of output row / column 0 onto input row / column 1: see the NCHW kernel)
+    auto row_sums = [&](const float *row, float (&t)[8]) {
+        float v[4][8];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) bg_ld8(row + (size_t)min(max(2 * x - 1 + b, 0), OW - 1) * 8, v[b]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)                      // the NCHW kernel's order per channel
+            t[k] = ((wx[0] * v[0][k] + wx[1] * v[1][k]) + wx[2] * v[2][k]) + wx[3] * v[3][k];
+        if (x == 1) {
+            float c0[8];
+            bg_ld8(row, c0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float z = 0.0f * c0[k];
+                if (z != z) t[k] = z;
+            }
+        }
+    };
     float r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int oy = 2 * y - 1 + a;
         const float wy = up_weight(oy, y, H);
-        const float *row = gp + (size_t)min(max(oy, 0), OH - 1) * OW * 8;
-        float v[4][8];
+        float t[8];
+        row_sums(gp + (size_t)min(max(oy, 0), OH - 1) * OW * 8, t);
 #pragma unroll
-        for (int b = 0; b < 4; ++b) bg_ld8(row + (size_t)min(max(2 * x - 1 + b, 0), OW - 1) * 8, v[b]);
+        for (int k = 0; k < 8; ++k) r[k] += wy * t[k];
+    }
+    if (y == 1) {
+        float t[8];
+        row_sums(gp, t);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {                    // the NCHW kernel's order per channel
-            const float t = ((wx[0] * v[0][k] + wx[1] * v[1][k]) + wx[2] * v[2][k]) + wx[3] * v[3][k];
-            r[k] += wy * t;
+        for (int k = 0; k < 8; ++k) {
+            const float z = 0.0f * t[k];
+            if (z != z) r[k] = z;
         }
     }
     bg_st8(gin + (plane * (size_t)H * W + idx) * 8, r);

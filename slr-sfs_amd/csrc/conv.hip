@@ -232,6 +232,8 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
             v = fmaxf(x * pss[g.cb + j] - pss[CV_MAXCIN + g.cb + j], 0.0f) * mk;
             g.cnt += (g.cb + j <= cmax) ? mk : 0.0f;     // (x != 0) inside the image, real channels only: the derived
                                                          // mask's channel sum
+        } else if (F32) {    // the training rung (mk0 is 1 or 0): the padding is a select -- the clamped address holds element 0 of the
+            v = g.mk0 != 0.0f ? x : 0.0f;                   // plane, and a NaN there must not reach every border pixel as 0 x NaN
         } else {
             v = x * g.mk0;
         }
@@ -514,7 +516,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
 #pragma unroll
                         for (int dx = 0; dx < 3; ++dx) box += mpl[(wp * PT + pt + dy) * CV_HW + (lane & 31) + dx];
                     const float u = box * mscale;
-                    const float um = fminf(fmaxf(u, 0.0f), 1.0f);
+                    const float um = F32 ? clamp01_nan(u) : fminf(fmaxf(u, 0.0f), 1.0f);      // (the training rung keeps a NaN mask NaN)
                     const float ratio = (1.0f / (u + 1e-8f)) * winsize * um;
                     const int oy = y0 + wp * PT + pt, ox = x0 + (lane & 31);
                     if (ox < a.W && oy < a.H && a.um_out && blockIdx.y == 0 && wc == 0 && lane < 32)
@@ -775,7 +777,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx) box += mpl[(wp * PT + pt + dy) * CV_HW + bcol + dx];
                 const float u = box * mscale;                      // exact small integers in fp32
-                const float um = fminf(fmaxf(u, 0.0f), 1.0f);
+                const float um = F32 ? clamp01_nan(u) : fminf(fmaxf(u, 0.0f), 1.0f);      // (the training rung keeps a NaN mask NaN)
                 const float ratio = (1.0f / (u + 1e-8f)) * winsize * um;       // torch: scalar / tensor = reciprocal * scalar
                 if (ok && a.um_out && ct == 0 && blockIdx.y == 0 && wc == 0 && bgrp == 0)
                     a.um_out[(size_t)n * HW + pix] = um;

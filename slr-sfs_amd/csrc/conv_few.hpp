@@ -165,7 +165,7 @@ __global__ __launch_bounds__(CF_THREADS, SKP && NCO < 4 ? 3 : 2) void conv3x3_fe
                     v = fmaxf(x * sc[j] - sh[j], 0.0f) * mk;
                     cnt[i] += (ch <= cmax) ? mk : 0.0f;    // (x != 0) inside the image, real channels only: the derived mask's channel sum
                 } else {
-                    v = x * mk0[i];
+                    v = mk0[i] != 0.0f ? x : 0.0f;        // (mk0 is 1 or 0 here; a select: a NaN at the clamped address stays out)
                 }
                 (&xs[j][0][0])[lds_at[i]] = v;
             }
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(CF_THREADS, SKP && NCO < 4 ? 3 : 2) void conv3x3_fe
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) box += mpl[(row + dy) * CF_HW + xq + p + dx];
             const float u = box * a.mask_scale;            // exact small integers in fp32
-            um[p] = fminf(fmaxf(u, 0.0f), 1.0f);
+            um[p] = clamp01_nan(u);
             ratio[p] = (1.0f / (u + 1e-8f)) * a.winsize * um[p];       // torch: scalar / tensor = reciprocal * scalar
         }
         if (a.um_out) {

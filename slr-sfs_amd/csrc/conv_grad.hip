@@ -85,7 +85,7 @@ __device__ __forceinline__ void wg_store(float *__restrict__ t, const WgRegs<B8,
 // grid (splits, ci tiles, co tiles).  Slab s takes the chunks [s T / S, (s + 1) T / S) of the T = N * ceil(H / 2) * ceil(W / 32) chunks in
 // row-major order and writes part[s][tap][co][ci].  One wave per SIMD: 144 accumulator registers + the next chunk's staging registers
 // (310 - 492 in all); the split rule launches about one workgroup per CU, so a second resident workgroup would rarely exist anyway.
-template <bool XB8, bool GB8>
+template <bool XB8, bool GB8, bool EDGE>
 __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__ G,
                                                                        float *__restrict__ part, int N, int Cin, int Cout, int H, int W,
                                                                        int chunks, int CY, int CX) {
@@ -120,7 +120,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_wgrad_kernel(const floa
         __syncthreads();
         if (ch + 1 < last) load_chunk(ch + 1);           // in flight during the MFMAs below
         // a k step = the pixel pair (x, x + 1) of one row; tap (ky, kx) reads X at row + ky, column + kx of the halo block.  The kx = 2
-        // operand of a pair is the kx = 0 operand of the next one.
+        // operand of a pair is the kx = 0 operand of the next one.  A G pixel of the chunk that lies outside the image is no term of the
+        // sum: its G is zero, and its X operands are SELECTED to zero too -- they are real elements of X (the halo of the image's last
+        // rows and columns), and 0 x NaN on the matrix core would put a NaN of theirs into taps it has no part in.  EDGE = false (the
+        // host: H % 2 == 0 and W % 32 == 0, no chunk reaches past the image) compiles the selects away: in this loop they cost 19 %.
+        const int rem = ch % per_image, cy = rem / CX, cx = rem - cy * CX;
+        const int rows_in = H - cy * WG_RH, cols_in = W - cx * WG_CW - h;    // this lane's pixel (ry, 2 xp + h) is inside iff ry < rows_in, 2 xp < cols_in
 #pragma unroll
         for (int ry = 0; ry < WG_RH; ++ry) {
             float carry[3];
@@ -129,15 +134,16 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_wgrad_kernel(const floa
 #pragma unroll
             for (int xp = 0; xp < WG_CW / 2; ++xp) {
                 const float a = ga[(ry * WG_CW + 2 * xp) * PSG];
+                const bool in = !EDGE || (ry < rows_in && 2 * xp < cols_in);
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky) {
-                    const float b0 = carry[ky];
                     const float b1 = xa[((ry + ky) * WG_XW + 2 * xp + 1) * PSX];
                     const float b2 = xa[((ry + ky) * WG_XW + 2 * xp + 2) * PSX];
+                    const float s0 = in ? carry[ky] : 0.0f, s1 = in ? b1 : 0.0f, s2 = in ? b2 : 0.0f;
                     carry[ky] = b2;
-                    acc[ky * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[ky * 3 + 0], 0, 0, 0);
-                    acc[ky * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[ky * 3 + 1], 0, 0, 0);
-                    acc[ky * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b2, acc[ky * 3 + 2], 0, 0, 0);
+                    acc[ky * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s0, acc[ky * 3 + 0], 0, 0, 0);
+                    acc[ky * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s1, acc[ky * 3 + 1], 0, 0, 0);
+                    acc[ky * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s2, acc[ky * 3 + 2], 0, 0, 0);
                 }
             }
         }
@@ -319,8 +325,14 @@ SLR_EXPORT int slr_conv3x3_weight_grad(const float *x, const float *g, float *dw
     float *part = (float *)((char *)ws + wg_bias_bytes(N, Cout, H, W));
     const dim3 grid(S, wg_tiles(Cin), wg_tiles(Cout));
     const int chunks = (int)wg_chunks(N, H, W), CY = (H + WG_RH - 1) / WG_RH, CX = (W + WG_CW - 1) / WG_CW;
-#define SLR_WGRAD_LAUNCH(XB, GB) \
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<XB, GB>), grid, dim3(WG_THREADS), 0, st, x, g, part, N, Cin, Cout, H, W, chunks, CY, CX)
+    const bool edge = H % WG_RH != 0 || W % WG_CW != 0;  // some chunk reaches past the image
+#define SLR_WGRAD_LAUNCH(XB, GB)                                                                                                              \
+    do {                                                                                                                                      \
+        if (edge) hipLaunchKernelGGL((conv3x3_wgrad_kernel<XB, GB, true>), grid, dim3(WG_THREADS), 0, st, x, g, part, N, Cin, Cout, H, W,    \
+                                     chunks, CY, CX);                                                                                         \
+        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<XB, GB, false>), grid, dim3(WG_THREADS), 0, st, x, g, part, N, Cin, Cout, H, W,        \
+                                chunks, CY, CX);                                                                                              \
+    } while (0)
     if (xb8 && gb8) SLR_WGRAD_LAUNCH(true, true);
     else if (xb8) SLR_WGRAD_LAUNCH(true, false);
     else if (gb8) SLR_WGRAD_LAUNCH(false, true);

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(BG_THREADS) void nz_forward_kernel(const float *__r
     bg_table<B8>(it, scale, it.n, C, sc);
     bg_table<B8>(it, shift, it.n, C, sh);
 #pragma unroll
-    for (int k = 0; k < K; ++k) e[k] = fmaxf(e[k] * sc[k] - sh[k], 0.0f) * (e[k] != 0.0f ? 1.0f : 0.0f);
+    for (int k = 0; k < K; ++k) e[k] = relu_nan(e[k] * sc[k] - sh[k]) * (e[k] != 0.0f ? 1.0f : 0.0f);      // (NaN stays NaN)
     bg_store<B8>(it, a, e);
 }
 
@@ -202,7 +202,7 @@ __device__ __forceinline__ void nz_gate(const BgItem<B8> &it, const float *__res
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const float y = e[k] * sc[k] - sh[k];
-        gy[k] = (y > 0.0f && e[k] != 0.0f) ? g[k] : 0.0f;
+        gy[k] = (y <= 0.0f || e[k] == 0.0f) ? 0.0f : g[k];      // (closed on `<= 0` only, as torch's ReLU backward: open for a NaN)
     }
 }
 

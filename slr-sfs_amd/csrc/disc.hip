@@ -58,13 +58,22 @@ __global__ __launch_bounds__(256) void conv4x4_wgrad_kernel(const float *__restr
             xs[(ry * XW + rx) * 33 + ci] = v;
         }
         __syncthreads();
-        const int npair = (cw + 1) >> 1;
+        const int npair = cw >> 1;
         for (int j = 0; j < npair; ++j) {
             const int pix = 2 * j + h;
             const float av = gs[pix * 33 + c];
             const float *xb = xs + ((ky * XW + S * pix) * 33 + c);
 #pragma unroll
             for (int kx = 0; kx < 4; ++kx) acc[kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xb[kx * 33], acc[kx], 0, 0, 0);
+        }
+        if (cw & 1) {
+            // the odd last pixel's partner is no term of the sum: its G is a staged zero and its X operands are selected to zero too, or
+            // 0 x NaN on the matrix core would put a NaN of a real X element into taps it has no part in
+            const int pix = cw - 1 + h;
+            const float av = gs[pix * 33 + c];
+            const float *xb = xs + ((ky * XW + S * pix) * 33 + c);
+#pragma unroll
+            for (int kx = 0; kx < 4; ++kx) acc[kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, h == 0 ? xb[kx * 33] : 0.0f, acc[kx], 0, 0, 0);
         }
     }
     // D[row = co][column = ci]: the column on the lane, row mfma32_row(q, lane >> 5) in register q

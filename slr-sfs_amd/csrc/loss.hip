@@ -70,17 +70,17 @@ __global__ __launch_bounds__(256) void loss_sum_finish_kernel(const double *__re
 
 // ------------------------------------------------------------------ slice distance + seed + ReLU gate
 // Per element of the raw feature a (prediction), b (ground truth) and the gradient g arriving from the layer above:
-//   d = relu(a) - relu(b);  sum += |d|;  out = a > 0 ? g + sign(d) * k : 0      (k = coef * gscale[0], formed once, fp32)
-// without b: out = a > 0 ? g : 0, the ReLU backward of a layer that ends no slice.  Every operation is the fp32 one torch would do.
+//   d = relu(a) - relu(b);  sum += |d|;  out = a <= 0 ? 0 : g + sign(d) * k     (k = coef * gscale[0], formed once, fp32)
+// without b: out = a <= 0 ? 0 : g, the ReLU backward of a layer that ends no slice.  Every operation is the fp32 one torch would do.
 template <bool HAS_B>
 __device__ __forceinline__ float gate_elem(float a, float b, float g, float k, double &sum) {
     float v = g;
     if (HAS_B) {
-        const float d = fmaxf(a, 0.0f) - fmaxf(b, 0.0f);
+        const float d = relu_nan(a) - relu_nan(b);       // (a NaN feature makes the sum NaN; sign(NaN) = 0, torch.sign's)
         sum += (double)fabsf(d);
         v = g + sign_of(d) * k;
     }
-    return a > 0.0f ? v : 0.0f;
+    return a <= 0.0f ? 0.0f : v;                         // torch's ReLU backward: closed on `<= 0` only, open for a NaN a
 }
 
 template <bool HAS_B>
@@ -116,15 +116,15 @@ __global__ __launch_bounds__(LS_THREADS) void feature_l1_gate_kernel(const float
 // ------------------------------------------------------------------ backward of ReLU + MaxPool2d(2, 2)
 // One thread per 2x2 window of the INPUT grid rounded up (so the last row / column of an odd H / W belongs to a thread too) and 8
 // channels: a complete window sends its pooled gradient to its first maximum in row-major order (torch's max_pool2d keeps the first:
-// it replaces on `>` only) if that maximum is > 0 (the ReLU), zero to the other three; an incomplete one (floor mode: not pooled)
-// writes zeros.  Every output element is written exactly once.
+// it replaces on `>` -- or on a NaN, so a window with NaNs sends it to its last NaN) if that maximum is > 0 or NaN (the ReLU), zero
+// to the other three; an incomplete one (floor mode: not pooled) writes zeros.  Every output element is written exactly once.
 __device__ __forceinline__ void route1(float x0, float x1, float x2, float x3, float g, float &o0, float &o1, float &o2, float &o3) {
     float best = x0;
     int at = 0;
-    if (x1 > best) { best = x1; at = 1; }
-    if (x2 > best) { best = x2; at = 2; }
-    if (x3 > best) { best = x3; at = 3; }
-    const float r = best > 0.0f ? g : 0.0f;
+    if (x1 > best || x1 != x1) { best = x1; at = 1; }    // torch's rule: replace on `>` or on a NaN -- the LAST NaN of a window wins
+    if (x2 > best || x2 != x2) { best = x2; at = 2; }
+    if (x3 > best || x3 != x3) { best = x3; at = 3; }
+    const float r = best <= 0.0f ? 0.0f : g;             // torch's ReLU backward: closed on `<= 0` only, so open for a NaN
     o0 = at == 0 ? r : 0.0f;
     o1 = at == 1 ? r : 0.0f;
     o2 = at == 2 ? r : 0.0f;

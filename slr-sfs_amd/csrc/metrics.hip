@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void vgg_prep_kernel(const void *__restrict__ 
 }
 
 // ------------------------------------------------------------------ ReLU + MaxPool2d(2, 2) on channel-blocked activations
-// nn.ReLU then nn.MaxPool2d(kernel_size=2, stride=2) of torchvision's vgg16.features: floor mode; max of relu = relu of max.
+// nn.ReLU then nn.MaxPool2d(kernel_size=2, stride=2) of torchvision's vgg16.features: floor mode; max of relu = relu of max.  The
+// training loss runs it too (losses.py), so a NaN in a window makes the window's output NaN, as torch's does (max_nan).
 __global__ __launch_bounds__(256) void relu_maxpool2_b8_kernel(const float4 *__restrict__ in, float4 *__restrict__ out, long long total,
                                                                int H, int W, int OH, int OW) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -203,8 +204,8 @@ __global__ __launch_bounds__(256) void relu_maxpool2_b8_kernel(const float4 *__r
 #pragma unroll
         for (int dx = 0; dx < 2; ++dx) {
             const float4 a = src[((size_t)dy * W + dx) * 2], b = src[((size_t)dy * W + dx) * 2 + 1];
-            lo.x = fmaxf(lo.x, a.x); lo.y = fmaxf(lo.y, a.y); lo.z = fmaxf(lo.z, a.z); lo.w = fmaxf(lo.w, a.w);
-            hi.x = fmaxf(hi.x, b.x); hi.y = fmaxf(hi.y, b.y); hi.z = fmaxf(hi.z, b.z); hi.w = fmaxf(hi.w, b.w);
+            lo.x = max_nan(lo.x, a.x); lo.y = max_nan(lo.y, a.y); lo.z = max_nan(lo.z, a.z); lo.w = max_nan(lo.w, a.w);
+            hi.x = max_nan(hi.x, b.x); hi.y = max_nan(hi.y, b.y); hi.z = max_nan(hi.z, b.z); hi.w = max_nan(hi.w, b.w);
         }
     out[i * 2] = lo;
     out[i * 2 + 1] = hi;

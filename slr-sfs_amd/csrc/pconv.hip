@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void pconv_epilogue_kernel(const V *__restrict
         const float *rf = reinterpret_cast<const float *>(&r);
 #pragma unroll
         for (int k = 0; k < L; ++k) {
-            const float um = fminf(fmaxf(uf[k], 0.0f), 1.0f);                // :66
+            const float um = clamp01_nan(uf[k]);                // :66
             // scalar / tensor is reciprocal(tensor) * scalar in torch (Tensor.__rtruediv__): same here
             const float ratio = (1.0f / (uf[k] + 1e-8f)) * winsize * um;     // :64,67
             float o = (vf[k] * ratio + b) * um;                              // :72-74
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void pconv_epilogue_kernel(const V *__restrict
             V m = u;
             float *mw = reinterpret_cast<float *>(&m);
 #pragma unroll
-            for (int k = 0; k < L; ++k) mw[k] = fminf(fmaxf(mw[k], 0.0f), 1.0f);
+            for (int k = 0; k < L; ++k) mw[k] = clamp01_nan(mw[k]);
             um_out[(size_t)n * HWv + i] = m;
         }
     }

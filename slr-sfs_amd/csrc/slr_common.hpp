@@ -55,6 +55,17 @@ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 __host__ __device__ constexpr int mfma32_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
+// ---- ReLU and max that keep a NaN (the training path) ------------------------------------------
+// fmaxf returns the other operand when one is a NaN, so fmaxf(NaN, 0) = 0; torch.relu, clamp and max_pool2d return the NaN, and the
+// training kernels follow torch.  On operands that are not NaN both give fmaxf's bits.
+__device__ __forceinline__ float max_nan(float a, float b) {
+    const float m = fmaxf(a, b);
+    return a != a ? a : (b != b ? b : m);
+}
+__device__ __forceinline__ float relu_nan(float x) { return x != x ? x : fmaxf(x, 0.0f); }
+// torch.clamp(x, 0, 1) of the partial convolution's update mask (partialconv2d.py:66): a NaN mask stays NaN
+__device__ __forceinline__ float clamp01_nan(float x) { return x != x ? x : fminf(fmaxf(x, 0.0f), 1.0f); }
+
 // ---- bilinear footprint ------------------------------------------------------------------
 // Restates models/softsplat.py:169-184 (target coordinate, NW corner, 4 weights).
 struct Corners {

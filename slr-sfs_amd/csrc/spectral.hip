@@ -6,7 +6,8 @@
 //   (a) spectral_sigma_kernel, one workgroup per matrix W [rows, cols] (weight_orig viewed as [Cout, Cin k k]); matrices of at least
 //       SLR_SPECTRAL_SPLIT_ELEMENTS elements are first cut into bands of SLR_SPECTRAL_BAND_ROWS rows, a workgroup per band, in two
 //       launches of their own (below), so that no single workgroup walks a large matrix alone:
-//         training:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (one power iteration, torch's order)
+//         training:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (one power iteration, torch's order; the max is
+//         torch.clamp's: a NaN norm stays NaN, so a NaN in W makes all of its u, v and sigma NaN)
 //         both:      inv_sigma = 1 / (u^T W v);  u and v are copied into the call's saved arrays for the backward.
 //       Phase 1 (W^T u) walks the rows with the lanes along the columns, four adjacent columns per lane; row groups are added in group
 //       order through LDS.  Phase 2 (W v) gives a row to a wave, the lanes along the columns again, and a butterfly over the wave.
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(SPEC_BAND_THREADS) void spectral_band_wv_kernel(cha
         block_sum<1, SPEC_BAND_WAVES>(sq, red);
         if (tid == 0) bcast = sq[0];
         __syncthreads();
-        const double nv = sqrt(bcast), dv = nv > eps ? nv : eps;
+        const double nv = sqrt(bcast), dv = nv <= eps ? eps : nv;
         for (int c = tid; c < C; c += SPEC_BAND_THREADS) {
             const float vc = (float)(tmp[c] / dv);
             vec[c] = vc;
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_sigma_kernel(const char
             __syncthreads();
         }
         const double nv = sqrt(spec_dot(tmp, nullptr, C, red, &bcast));
-        const double dv = nv > eps ? nv : eps;
+        const double dv = nv <= eps ? eps : nv;
         for (int c = tid; c < C; c += SPEC_THREADS) {
             const float vc = (float)(tmp[c] / dv);
             vec[c] = vc;
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_sigma_kernel(const char
     double sigma;
     if (training) {
         const double nu = sqrt(spec_dot(tmp, nullptr, R, red, &bcast));
-        const double du = nu > eps ? nu : eps;
+        const double du = nu <= eps ? eps : nu;
         for (int r = tid; r < R; r += SPEC_THREADS) {
             const float ur = (float)(tmp[r] / du);
             vec[r] = ur;                               // (v is no longer needed)

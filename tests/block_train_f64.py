@@ -58,7 +58,9 @@ def bn_train_grads(x, mask, gain, bias, ga, eps=EPS, stored=None, addend=None):
         m, v, cnt = bn_stats(x, mask, eps)
     scale, shift = bn_tables(m, v, gain, bias, eps)
     y = bn_gate(x, scale, shift, mask)[0]
-    gy = (ga if mask is None else ga * mask) * (y > 0).to(x.dtype)
+    gm = ga if mask is None else ga * mask
+    gy = torch.where(y <= 0, torch.zeros_like(gm), gm)   # (torch's ReLU backward: a select, closed on `<= 0` only -- a NaN arriving at a
+                                                         #  closed gate stops, a NaN pre-activation leaves the gate open)
     rs = torch.rsqrt(v + eps)
     s0, s1 = gy.sum((2, 3)), (gy * x).sum((2, 3))
     dbias, dgain = s0, rs[None] * (s1 - m[None] * s0)

@@ -49,7 +49,7 @@ def bn_nz_train_grads(x, gain, bias, ga, eps=EPS, stored=None, addend=None):
         m, v, cnt = bn_nz_stats(x, eps)
     scale, shift = B64.bn_tables(m, v, gain, bias, eps)
     y = x * _t(scale) - _t(shift)
-    gy = ga * kept(x) * (y > 0).to(x.dtype)
+    gy = torch.where((y <= 0) | (x == 0), torch.zeros_like(ga), ga)     # (torch's ReLU backward: a select, closed on `<= 0` only)
     rs = torch.rsqrt(v + eps)
     s0, s1 = gy.sum((2, 3)), (gy * x).sum((2, 3))
     dbias, dgain = s0, rs[None] * (s1 - m[None] * s0)
