@@ -27,7 +27,8 @@
 //     global memory one tap ahead (1 KiB contiguous per fragment, L2-resident);
 //   * a wave owns CPW 32-channel tiles x PT rows: CPW x PT accumulator tiles of 32x32 (128-channel
 //     variant: wave wc = one channel tile x all 8 rows, 128 registers), 3 MFMAs per tile, tap and
-//     chunk; the B fragments of the rows are read in two batches of four against the same A;
+//     chunk; the B fragments of the rows are read in two batches of four against the same A, each batch requested under the
+//     MFMAs of the batch before it (one software pipeline per chunk, see the main loop);
 //   * epilogue on the accumulators: plain (+bias) or the partial-convolution one
 //     (o = (raw*ratio + b)*um, then + residual or the next layer's relu(bn(.))*um), same operations
 //     in the same order as csrc/pconv.hip.  The D layout (row = channel, column = pixel) makes every
@@ -224,12 +225,13 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
         g.mk0 = R.value < 2 ? mA : mB;
         g.cnt = 0.0f;
     };
-    auto stage_value = [&](int j, Stage &g, const float (&st)[8]) {
+    // psc / psh: the value's prologue scale and shift where the caller has fetched them ahead (the split rung's main loop), else null
+    auto stage_value = [&](int j, Stage &g, const float (&st)[8], const float *psc = nullptr, const float *psh = nullptr) {
         const float x = st[j];
         float v;
         if (PRE) {           // scale / shift are read per value (2 broadcast LDS reads) rather than held in 16 registers
             const float mk = (nonzero_mask & (x == 0.0f)) ? 0.0f : g.mk0;
-            v = fmaxf(x * pss[g.cb + j] - pss[CV_MAXCIN + g.cb + j], 0.0f) * mk;
+            v = fmaxf(x * (psc ? psc[j] : pss[g.cb + j]) - (psh ? psh[j] : pss[CV_MAXCIN + g.cb + j]), 0.0f) * mk;
             g.cnt += (g.cb + j <= cmax) ? mk : 0.0f;     // (x != 0) inside the image, real channels only: the derived
                                                          // mask's channel sum
         } else if (F32) {    // the training rung (mk0 is 1 or 0): the padding is a select -- the clamped address holds element 0 of the
@@ -324,8 +326,15 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
     // them (memory latency, not L2 latency), and one tap of these kernels is shorter than that
     h8 a_nx2[DEEP ? CPW : 1][2];
     if (DEEP) { load_a(a_nxt, min(1, glast)); }
+    // B fragments are read in batches of <= 4 pixel tiles (32 registers): a wave with 8 rows (WCO = 4) makes two passes per tap with
+    // the same A fragments.  The batches of a chunk form one software pipeline (split rung): see the tap below.
+    constexpr int PB = PT > 4 ? 4 : PT, NB = PT / PB;
+    constexpr int PSA = 2;                             // prologue scale / shift of a staged value: requested this many values ahead
     for (int c = 0; c < nchunk; ++c) {
         const int buf = c & 1;
+        h8 bx[2][PB];                                  // the two register sets the batches' hi / lo fragments rotate through
+        constexpr bool PSAHEAD = PRE && !F32;
+        float psc[PSAHEAD ? 8 : 1], psh[PSAHEAD ? 8 : 1];
         const int cn = min(c + 1, nchunk - 1);         // the chunk staged under this one's MFMAs (the last
                                                        // iteration re-stages its own chunk: harmless, and it keeps
                                                        // every load unconditional -> counted vmcnt waits)
@@ -334,7 +343,8 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
         for (int tap = 0; tap < 9; ++tap) {
             const int kh = tap / 3, kw = tap - kh * 3;
             // keeps the B fragments of different taps from being kept live together (the 36 distinct
-            // ones of a chunk would take 144 registers and spill); LDS has the bandwidth to re-read them
+            // ones of a chunk would take 144 registers and spill); LDS has the bandwidth to re-read them.  One batch crosses
+            // it in registers: this tap's first, requested under the last MFMAs of the tap before (split rung, below)
             asm volatile("" ::: "memory");
             // staging of the next chunk, one round per three taps: 8 registers in flight instead of 24.
             // A round's loads are issued at the top of taps 0 / 3 / 6 (behind the weight loads) and consumed
@@ -366,9 +376,6 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
             // consecutive MFMAs never touch the same accumulator.  In a staging tap the 8 values of the
             // round are converted BETWEEN groups of MFMAs (order pinned by scheduling barriers), so that
             // VALU work issues in the shadow of the matrix pipe instead of in front of it.
-            // B fragments are read in batches of <= 4 pixel tiles (32 registers): a wave with 8 rows
-            // (WCO = 4) makes two passes with the same A fragments.
-            constexpr int PB = PT > 4 ? 4 : PT, NB = PT / PB;
             constexpr int NM = 3 * CPW * PT, NMB = 3 * CPW * PB;
             if constexpr (F32) {
                 // 8 k-pairs x PT rows: MFMA (kp, row) multiplies the tap's weights of input channels 2kp, 2kp + 1 (lanes 0-31 / 32-63) with
@@ -396,30 +403,59 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
                         }
                     }
                 }
-            } else
+            } else {
+                // The batches of a chunk are one software pipeline: the fragments of batch n + 1 are requested under the MFMAs of batch n,
+                // each into the register its predecessor has just left -- a batch's lo fragment k is dead behind its w_hi x_lo product and
+                // takes the next batch's hi fragment, its hi fragment is dead behind w_hi x_hi and takes the next lo one -- so every read
+                // is issued 2 PB MFMAs ahead of its first use, across the tap boundary too (one batch is in flight over the fence at the
+                // top of a tap), and the order is pinned MFMA by MFMA.  Only a chunk's first batch is read where it is used: its buffer
+                // is complete behind the chunk barrier.  Per accumulator the order of the products is what it was.
+                // Prologue scale / shift of the staged values: PSA values ahead, so their waits are counted ones (LDS returns in order:
+                // a wait for a read just issued would drain every fragment read in flight with it).
+                // The first PSA of a round are requested in the tap before, in front of its last PB fragment reads.
+                const int pcb = cn * 16 + (tap / 3 < 2 ? tap / 3 * 8 : gB * 8);       // (= sg.cb of the staging tap this tap is or precedes)
+                auto ps_load = [&](int j) {
+                    if constexpr (PSAHEAD) { psc[j] = pss[pcb + j]; psh[j] = pss[CV_MAXCIN + pcb + j]; }
+                };
+                auto frag = [&](int t, int b, int k) { return (wp * PT + b * PB + k + t / 3) * CV_HW + t % 3 + bcol; };
 #pragma unroll
-            for (int hb = 0; hb < NB; ++hb) {
-                h8 bh[PB], bl[PB];
+                for (int hb = 0; hb < NB; ++hb) {
+                    const int q = (tap * NB + hb) & 1;
+                    h8 (&bh)[PB] = bx[q], (&bl)[PB] = bx[q ^ 1];
+                    if (tap == 0 && hb == 0) {
 #pragma unroll
-                for (int k = 0; k < PB; ++k) {
-                    const int p = (wp * PT + hb * PB + k + kh) * CV_HW + kw + bcol;
-                    bh[k] = xh[p];
-                    bl[k] = xl[p];
-                }
-#pragma unroll
-                for (int ib = 0; ib < NMB; ++ib) {
-                    const int part = ib / (CPW * PB), k = (ib / CPW) % PB, ct = ib % CPW;
-                    const int pt = hb * PB + k, i = hb * NMB + ib;
-                    const h8 av = part == 0 ? a_cur[ct][1] : a_cur[ct][0];
-                    const h8 bv = part == 1 ? bl[k] : bh[k];
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc[ct][pt], 0, 0, 0);
-                    if (stage_tap) {
-                        const int j0 = i * 8 / NM, j1 = (i + 1) * 8 / NM;
-                        if (j1 > j0) {
-#pragma unroll
-                            for (int j = j0; j < j1; ++j) stage_value(j, sg, stx[DEEP ? tap / 3 : 0]);
-                            __builtin_amdgcn_sched_barrier(0);
+                        for (int k = 0; k < PB; ++k) {
+                            bh[k] = xh[frag(0, 0, k)];
+                            bl[k] = xl[frag(0, 0, k)];
                         }
+                    }
+                    const bool more = tap < 8 || hb + 1 < NB;
+                    const int ntap = hb + 1 < NB ? tap : tap + 1, nhb = hb + 1 < NB ? hb + 1 : 0;
+#pragma unroll
+                    for (int ib = 0; ib < NMB; ++ib) {
+                        const int part = ib / (CPW * PB), k = (ib / CPW) % PB, ct = ib % CPW;
+                        const int pt = hb * PB + k, i = hb * NMB + ib;
+                        const h8 av = part == 0 ? a_cur[ct][1] : a_cur[ct][0];
+                        const h8 bv = part == 1 ? bl[k] : bh[k];
+                        acc[ct][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc[ct][pt], 0, 0, 0);
+                        if (more && ct == CPW - 1) {
+                            if (part == 1) bl[k] = xh[frag(ntap, nhb, k)];      // the next batch's hi fragment k
+                            if (part == 2) bh[k] = xl[frag(ntap, nhb, k)];      // ... and its lo fragment
+                        }
+                        if (tap % 3 == 1 && i == NM - PB - 1) {
+#pragma unroll
+                            for (int j = 0; j < PSA; ++j) ps_load(j);
+                        }
+                        if (stage_tap) {
+                            const int j0 = i * 8 / NM, j1 = (i + 1) * 8 / NM;
+#pragma unroll
+                            for (int j = j0; j < j1; ++j) {
+                                if (j + PSA < 8) ps_load(j + PSA);
+                                if constexpr (PSAHEAD) stage_value(j, sg, stx[DEEP ? tap / 3 : 0], psc, psh);
+                                else stage_value(j, sg, stx[DEEP ? tap / 3 : 0]);
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             }

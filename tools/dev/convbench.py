@@ -30,7 +30,7 @@ def split_weights(w):
 def conv_hip(x, buf, wscale, cout):
     n, cin, h, w = x.shape
     out = torch.empty(n, cout, h, w, device=x.device)
-    _lib.check(L.slr_conv3x3_forward(_lib.ptr(x), _lib.ptr(buf), None, None, _lib.ptr(out), n, cin, cout, h, w, wscale,
+    _lib.check(L.slr_conv3x3_forward(_lib.ptr(x), _lib.ptr(buf), None, None, _lib.ptr(out), n, cin, cout, h, w, wscale, 64.0,
                                      None, None, 0, _lib.stream_of(x)), "conv")
     return out
 
