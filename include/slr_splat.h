@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 22
+#define SLR_ABI_VERSION 23
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -981,6 +981,62 @@ int slr_spectral_grad_plan_fill(void *host_buf, size_t bytes, int n, const unsig
  * list.  No atomics, nothing synchronises. */
 int slr_spectral_weight_grad_multi(void *plan_dev, int n_tensors, int n_work, const float *inv_sigma, const float *saved_u,
                                    const float *saved_v, void *stream);
+
+/* ------------------------------------------------------------------ training the SPADE motion U-Net (ABI 23; csrc/motion_grad.hip, csrc/conv4x4.hip, csrc/disc.hip)
+ * The backward of the motion U-Nets' kernels above and the motion losses (models/losses/synthesis.py:11-58, 142-160), as the reference's
+ * train_motion_unet.py needs them.  All tensors NCHW fp32; nothing synchronises; no atomics: every long sum is accumulated in double in a
+ * fixed order, the same bits from run to run. */
+
+/* The encoder convolution Conv2d(Cin, Cout, 4, stride 2, padding 1) with leaky_relu(., slope) of its input (slr_conv4x4s2_forward).
+ * Forward in training: slr_conv4x4s2_forward on the fragments of slr_conv4x4_f32_weights(w, scale, ., Cout, Cin, 2, 0) (the layout of
+ * slr_conv4x4s2_f32_weights, every weight times the device scalar `scale`).
+ *
+ * slr_conv4x4s2_backward_data: gin [N,Cin,H,W] from g [N,Cout,(H-2)/2+1,(W-2)/2+1] as a gather, every element stored once.  Pixel
+ * (2a + py, 2b + px) gets the taps ky = (1 - py) + 2 ty, kx = (1 - px) + 2 tx reading g[a + py - ty][b + px - tx]: the taps of parity
+ * class (1 - py, 1 - px) of the padding-2 convolution, so `wfrag` is what slr_conv4x4_f32_weights(w, scale, ., Cout, Cin, 2, 1) prepares
+ * (slr_conv4x4_weight_bytes(Cout, Cin, 1) bytes) and the kernel reads it with the class bits flipped.  xin: the convolution's RAW input
+ * [N,Cin,H,W] when the layer has the LeakyReLU in front (the result is multiplied by xin > 0 ? 1 : slope), NULL when it has none (conv1).
+ * H, W >= 2, odd sizes included. */
+int slr_conv4x4s2_backward_data(const float *g, const float *xin, const void *wfrag, float *gin, int N, int Cin, int Cout, int H, int W,
+                                float slope, void *stream);
+
+/* dw[co][ci][ky][kx] = sum over (n, oy, ox) of g[n,co,oy,ox] * pre(x)[n,ci,2oy+ky-1,2ox+kx-1] (zero outside), pre = leaky_relu(., slope)
+ * when `leaky`, applied while staging; db[co] = sum of g in double (db NULL: not computed).  The slab scheme of slr_conv4x4_weight_grad:
+ * `splits` slabs of output pixels (0: chosen by the library), partial sums per slab in ws, a second launch adds them in double in slab
+ * order.  ws: 256-byte aligned, slr_conv4x4s2_grad_ws_bytes bytes (0 for sizes it refuses), else SLR_E_WORKSPACE. */
+size_t slr_conv4x4s2_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int splits);
+int slr_conv4x4s2_weight_grad(const float *x, const float *g, float *dw, float *db, int N, int Cin, int Cout, int H, int W, int leaky,
+                              float slope, int splits, void *ws, size_t ws_bytes, void *stream);
+
+/* slr_instnorm_spade that also keeps mean and rstd [N*C] of every plane for the backward: the same kernel code, so `out` is BIT-EQUAL to
+ * slr_instnorm_spade's (an eval() forward of the trainable network is the inference network's).  Planes of at least 2 x 2. */
+int slr_instnorm_spade_train_forward(const float *x, const float *gamma_beta, float *out, float *mean, float *rstd, int N, int C, int H,
+                                     int W, float eps, void *stream);
+
+/* From g = d out, with xh = (x - mean) rstd:  d beta = g,  d gamma = g xh,  gh = g (1 + gamma),
+ *   gx = rstd (gh - mean(gh) - xh mean(gh xh)),  the two means per plane from double sums;
+ * dgamma_beta [N,2C,H,W] = d gamma | d beta in gamma_beta's layout.  One workgroup per (n, c) plane. */
+int slr_instnorm_spade_backward(const float *x, const float *gamma_beta, const float *g, const float *mean, const float *rstd, float *gx,
+                                float *dgamma_beta, int N, int C, int H, int W, void *stream);
+
+/* The gradient of slr_upsample2x_concat: g [N,Ca+Cb,2H,2W] -> ga [N,Ca,H,W], gb [N,Cb,H,W] (Cb = 0: b, gb unused).  Every source pixel
+ * sums the <= 4 x 4 output pixels it feeds with the bilinear weights .25 / .75 and the edge clamping folded in (channel `nearest_channel`
+ * of each source: its 2 x 2 block).  relu = 1: the sum is gated by the source, a / b > 0 (a, b required); relu = 2: every g is gated by
+ * fwd > 0, fwd [N,Ca+Cb,2H,2W] the forward's result (required); relu'(0) = 0 as in torch.  relu = 0: a, b and fwd may be NULL. */
+int slr_upsample2x_concat_backward(const float *g, const float *fwd, const float *a, int Ca, const float *b, int Cb, float *ga, float *gb,
+                                   int N, int H, int W, int nearest_channel, int relu, void *stream);
+
+/* The motion losses in one pass over pred, gt [N,2,H,W], d = pred - gt:  sums [N][3] (DOUBLE, device) per image =
+ *   sum |d|_2  (EndPointError = its total / (N H W)),  sum |d_0| + |d_1|  (MotionL1 = total / (2 N H W)),  sum |d|_2^2  (PSNR's mse_err =
+ *   per image / (H W)).  Workgroups of 4096 pixels write partial sums to ws, a second launch adds them in order.
+ * ws: 256-byte aligned, slr_motion_loss_ws_bytes bytes (0 for sizes it refuses), else SLR_E_WORKSPACE. */
+size_t slr_motion_loss_ws_bytes(int N, int H, int W);
+int slr_motion_loss(const float *pred, const float *gt, double *sums, int N, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* gpred [N,2,H,W] = w_epe[0] d / |d|_2 / (N H W)  (exactly 0 where |d|_2 = 0: torch's norm backward)  +  w_l1[0] sign(d) / (2 N H W);
+ * w_epe, w_l1: DEVICE scalars (the gradients reaching the two means), either may be NULL (that term is absent). */
+int slr_motion_loss_grad(const float *pred, const float *gt, const float *w_epe, const float *w_l1, float *gpred, int N, int H, int W,
+                         void *stream);
 
 #ifdef __cplusplus
 }

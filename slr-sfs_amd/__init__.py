@@ -24,6 +24,9 @@ from .adversarial import (conv4x4, instnorm_lrelu, spectral_weight, TrainableNLa
 from .optim import Adam, TrainingOptimizers  # noqa: F401
 from .spectral import SpectralGroup, SpectralLinear, spectral_sigma, prepare_scaled, spectral_weight_grad, load_spectral_state_dict, reference_state_dict  # noqa: F401
 from .spectral import spectral_weight_grad_multi, defer_weight_grad  # noqa: F401
+from . import motion_training  # noqa: F401
+from .motion_training import (conv4x4s2, instnorm_spade_train, upsample2x_concat_train, motion_losses, MotionLoss,  # noqa: F401
+                              TrainableSPADEIN, TrainableSPADEUnet4MaskMotion, MotionTrainingModel)
 from . import model  # noqa: F401
 from .model import TrainingModel, Trainer  # noqa: F401
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 22
+ABI_VERSION = 23
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -133,6 +133,15 @@ SIGNATURES = {
     "slr_spectral_grad_plan_bytes": (_sz, [_i, _vp, _vp]),
     "slr_spectral_grad_plan_fill": (_i, [_vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slr_spectral_weight_grad_multi": (_i, [_vp, _i, _i, _fp, _fp, _fp, _vp]),
+    "slr_conv4x4s2_backward_data": (_i, [_fp, _fp, _vp, _fp, _i, _i, _i, _i, _i, _f, _vp]),
+    "slr_conv4x4s2_grad_ws_bytes": (_sz, [_i] * 6),
+    "slr_conv4x4s2_weight_grad": (_i, [_fp] * 4 + [_i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
+    "slr_instnorm_spade_train_forward": (_i, [_fp] * 5 + [_i, _i, _i, _i, _f, _vp]),
+    "slr_instnorm_spade_backward": (_i, [_fp] * 7 + [_i, _i, _i, _i, _vp]),
+    "slr_upsample2x_concat_backward": (_i, [_fp, _fp, _fp, _i, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_motion_loss_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_motion_loss": (_i, [_fp, _fp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_motion_loss_grad": (_i, [_fp] * 5 + [_i, _i, _i, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

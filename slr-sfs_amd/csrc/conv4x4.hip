@@ -23,6 +23,9 @@ namespace slr {
 //   C4_BWD2            gin = the stride-2 adjoint.  Pixel (iy, ix) = (2a + py, 2b + px) of parity class (py, px) = blockIdx.z gets the taps
 //                      ky = py + 2 ty, kx = px + 2 tx (the ones for which (iy + 2 - ky) / 2 is exact): 2 steps per co; step s: ty = s,
 //                      tx = l >> 5 reads g[a + 1 - ty][b + 1 - tx].  A tile's 32 pixels are of one class, so they share the A fragment.
+//   C4_ENCB2           gin = the adjoint of C4_ENC2 (stride 2, padding 1): iy = 2 oy - 1 + ky, so class (py, px) gets the taps
+//                      ky = (1 - py) + 2 ty, kx = (1 - px) + 2 tx and reads g[a + py - ty][b + px - tx].  Those are the taps of C4_BWD2's
+//                      class (1 - py, 1 - px): the C4_BWD2 fragments serve, read at class cls ^ 3 -- no preparation of its own.
 // Weight fragments (one coalesced 256-byte load per MFMA), T = ceil(produced channels / 32), zero beyond the last channel:
 //   forward   wf[((ct Cin + ci) 8 + s) 64 + l]                = w[32 ct + (l & 31)][ci][s >> 1][2 (s & 1) + (l >> 5)] * scale
 //   C4_BWD1   wf[((ct Cout + co) 8 + s) 64 + l]               = w[co][32 ct + (l & 31)][3 - (s >> 1)][3 - 2 (s & 1) - (l >> 5)] * scale
@@ -30,7 +33,7 @@ namespace slr {
 // scale: a device scalar or none -- the 1 / sigma of spectral normalisation costs no pass of its own and no host synchronisation.
 // (tools/disc_train_bench.py sorts the kernels of a trace by the first template argument: 0 / 1 forward, 2 / 3 backward-data of the
 // discriminator; C4_ENC2 is neither.)
-enum { C4_FWD1 = 0, C4_FWD2 = 1, C4_BWD1 = 2, C4_BWD2 = 3, C4_ENC2 = 4 };
+enum { C4_FWD1 = 0, C4_FWD2 = 1, C4_BWD1 = 2, C4_BWD2 = 3, C4_ENC2 = 4, C4_ENCB2 = 5 };
 
 __global__ __launch_bounds__(256) void conv4x4_weights_kernel(const float *__restrict__ w, const float *__restrict__ scale,
                                                               float *__restrict__ wf, int Cout, int Cin, int mode, long long total) {
@@ -82,7 +85,9 @@ __global__ __launch_bounds__(256) void conv4x4_weights_kernel(const float *__res
 // F: C4_FWD1 / C4_FWD2 -- LeakyReLU of the output; C4_ENC2 -- LeakyReLU of the value read (leaky_relu(0) = 0: zero padding before or
 // after it is the same); backward -- the value read is g * (gate > 0 ? 1 : slope) with `gate` a tensor of g's shape (the LeakyReLU output
 // of the layer whose gradient this is).  Epilogue: C4_FWD1 / C4_FWD2 add `bias` if there is one; C4_ENC2 adds bias or 0, then
-// y * post_scale[c] + post_shift[c] if there is a scale.  Every mode reads only its own pointers; MODE and F are resolved at compile time.
+// y * post_scale[c] + post_shift[c] if there is a scale; C4_ENCB2 -- F: the result times (gate > 0 ? 1 : slope) with `gate` the raw input
+// of the convolution, a tensor of gin's shape (the LeakyReLU sits in front of the encoder convolution, so its gate is applied to what is
+// produced, not to what is read).  Every mode reads only its own pointers; MODE and F are resolved at compile time.
 template <int MODE, int CT, bool F>
 __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__ in, const float *__restrict__ gate,
                                                        const float *__restrict__ wf, const float *__restrict__ bias,
@@ -90,12 +95,14 @@ __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__
                                                        float *__restrict__ out, int N, int Ck, int Cm, int IH, int IW, int OH, int OW,
                                                        float slope) {
     constexpr bool BWD = MODE == C4_BWD1 || MODE == C4_BWD2;
-    constexpr int NS = MODE == C4_BWD2 ? 2 : 8;
+    constexpr bool PAR = MODE == C4_BWD2 || MODE == C4_ENCB2;   // one launch per parity class of the produced pixels
+    constexpr int NS = PAR ? 2 : 8;
     extern __shared__ float red[];                       // [KW-1][CT*16][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, KW = blockDim.x >> 6;
-    const int cls = MODE == C4_BWD2 ? blockIdx.z : 0, py = cls >> 1, px = cls & 1;
+    const int cls = PAR ? blockIdx.z : 0, py = cls >> 1, px = cls & 1;
+    const int wcls = MODE == C4_ENCB2 ? cls ^ 3 : cls;   // the class whose weight fragments hold this class's taps
     // the pixel grid of this launch: the whole produced tensor, or its pixels of one parity class
-    const int PH = MODE == C4_BWD2 ? (OH - py + 1) / 2 : OH, PW = MODE == C4_BWD2 ? (OW - px + 1) / 2 : OW;
+    const int PH = PAR ? (OH - py + 1) / 2 : OH, PW = PAR ? (OW - px + 1) / 2 : OW;
     const int PHW = PH * PW;
     const long long P = (long long)N * PHW;
     if ((long long)blockIdx.x * 32 >= P) return;         // (uniform over the workgroup; an empty class has P = 0)
@@ -112,6 +119,9 @@ __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__
         if (MODE == C4_BWD2) {
             iy = a + 1 - s;
             ix = b + 1 - h;
+        } else if (MODE == C4_ENCB2) {
+            iy = a + py - s;
+            ix = b + px - h;
         } else {
             const int S = MODE == C4_FWD1 || MODE == C4_BWD1 ? 1 : 2, PAD = MODE == C4_FWD1 || MODE == C4_FWD2 ? 2 : 1;
             iy = S * a - PAD + (s >> 1);
@@ -141,7 +151,7 @@ __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__
         }
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
-            const float *af = wf + (((size_t)cls * T + ct0 + t) * Ck + c) * (NS * 64) + lane;
+            const float *af = wf + (((size_t)wcls * T + ct0 + t) * Ck + c) * (NS * 64) + lane;
 #pragma unroll
             for (int s = 0; s < NS; ++s) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s * 64], bv[s], acc[t], 0, 0, 0);
         }
@@ -166,7 +176,8 @@ __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__
     }
     if (!pv) return;
     const size_t OHW = (size_t)OH * OW;
-    float *op = out + (size_t)n * Cm * OHW + (MODE == C4_BWD2 ? (size_t)(2 * a + py) * OW + 2 * b + px : (size_t)r);
+    const size_t o0 = (size_t)n * Cm * OHW + (PAR ? (size_t)(2 * a + py) * OW + 2 * b + px : (size_t)r);
+    float *op = out + o0;
 #pragma unroll
     for (int t = 0; t < CT; ++t)
 #pragma unroll
@@ -177,6 +188,8 @@ __global__ __launch_bounds__(1024) void conv4x4_kernel(const float *__restrict__
                 if (MODE == C4_ENC2) {
                     y = y + (bias ? bias[cm] : 0.0f);        // (+ 0 without a bias: -0 leaves as +0)
                     if (post_scale) y = y * post_scale[cm] + post_shift[cm];
+                } else if (MODE == C4_ENCB2) {
+                    if (F) y *= gate[o0 + (size_t)cm * OHW] > 0.0f ? 1.0f : slope;
                 } else if (!BWD) {
                     if (bias) y += bias[cm];
                     if (F) y = y > 0.0f ? y : y * slope;
@@ -196,7 +209,7 @@ static void c4_launch(const float *in, const float *gate, const float *wf, const
     // CT channel tiles per workgroup (the taps are loaded once for all of them); launches of a few tiles take one and split K over up to
     // 16 waves instead, so that the deep layers fill the chip.  LDS of the K split: (KW - 1) * CT * 4 KiB <= 60 KiB.
     int CT = ntile % 4 == 0 ? 4 : ntile % 2 == 0 ? 2 : 1;
-    const int classes = MODE == C4_BWD2 ? 4 : 1;
+    const int classes = MODE == C4_BWD2 || MODE == C4_ENCB2 ? 4 : 1;
     if (ptiles * classes * (ntile / CT) < 512) CT = 1;
     const long long wgs = ptiles * classes * (ntile / CT);
     int KW = 1;
@@ -257,6 +270,25 @@ SLR_EXPORT int slr_conv4x4s2_forward(const float *in, const void *wfrag, const f
     SLR_CHECK_ARG((pixels + 31) / 32 < (1LL << 31), "sizes");
     c4_launch_if<C4_ENC2>(leaky != 0, in, nullptr, (const float *)wfrag, bias, post_scale, post_shift, out, N, Cin, Cout, H, W, OH, OW, pixels,
                        slope, (hipStream_t)stream);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+static bool e4_sizes_ok(int N, int Cin, int Cout, int H, int W) {
+    return N > 0 && N < 65536 && Cin > 0 && Cin < (1 << 16) && Cout > 0 && Cout < (1 << 16) && H >= 2 && W >= 2 && H < (1 << 20) && W < (1 << 20) &&
+           (long long)H * W < (1LL << 31) && (long long)N * H * W < (1LL << 31) && (long long)N * Cin * H * W < (1LL << 40);
+}
+
+SLR_EXPORT int slr_conv4x4s2_backward_data(const float *g, const float *xin, const void *wfrag, float *gin, int N, int Cin, int Cout, int H,
+                                           int W, float slope, void *stream) {
+    SLR_CHECK_ARG(g && wfrag && gin, "null pointer");
+    SLR_CHECK_ARG(e4_sizes_ok(N, Cin, Cout, H, W), "sizes (H, W >= 2)");
+    SLR_CHECK_ARG(!(((uintptr_t)g | (uintptr_t)xin | (uintptr_t)wfrag | (uintptr_t)gin) & 3), "4-byte aligned tensors");
+    const int OH = (H - 2) / 2 + 1, OW = (W - 2) / 2 + 1;
+    const float *none = nullptr;
+    const long long pixels = (long long)N * ((H + 1) / 2) * ((W + 1) / 2);   // the even-even class, the largest
+    c4_launch_if<C4_ENCB2>(xin != nullptr, g, xin, (const float *)wfrag, none, none, none, gin, N, Cout, Cin, OH, OW, H, W, pixels, slope,
+                           (hipStream_t)stream);
     SLR_CHECK_LAUNCH();
     return 0;
 }

@@ -19,7 +19,9 @@ namespace slr {
 // staged in LDS as [pixel][channel] (stride 33: conflict-free for both the staging stores and the operand reads).  A k step is a pixel
 // pair; a chunk of cw pixels takes ceil(cw / 2) steps (an odd last pixel pairs with a staged zero).  Slab s takes the chunks
 // [s T / S, (s + 1) T / S) of the T = N * OH * ceil(OW / 32) in row-major order and writes part[s][co][ci][ky][kx].
-template <int S>
+// PAD: the convolution's padding (2: the discriminator; 1: the motion encoder, slr_conv4x4s2_weight_grad).  PRO: the convolution reads
+// leaky_relu(X, slope) -- applied while staging (leaky_relu(0) = 0: the zero padding is the same before or after it).
+template <int S, int PAD = 2, bool PRO = false>
 __global__ __launch_bounds__(256) void conv4x4_wgrad_kernel(const float *__restrict__ X, const float *__restrict__ G,
                                                             const float *__restrict__ gate, float *__restrict__ part, int N, int Cin,
                                                             int Cout, int H, int W, int OH, int OW, int chunks, int CX, float slope) {
@@ -52,9 +54,10 @@ __global__ __launch_bounds__(256) void conv4x4_wgrad_kernel(const float *__restr
         }
         for (int item = threadIdx.x; item < 32 * 4 * XW; item += 256) {
             const int ci = item / (4 * XW), rr = item - ci * (4 * XW), ry = rr / XW, rx = rr - ry * XW;
-            const int iy = S * oy + ry - 2, ix = S * ox0 + rx - 2;
+            const int iy = S * oy + ry - PAD, ix = S * ox0 + rx - PAD;
             float v = 0.0f;
             if (iy >= 0 && iy < H && ix >= 0 && ix < W && ci0 + ci < Cin) v = X[(((size_t)n * Cin + ci0 + ci) * H + iy) * W + ix];
+            if (PRO) v = v > 0.0f ? v : v * slope;
             xs[(ry * XW + rx) * 33 + ci] = v;
         }
         __syncthreads();
@@ -123,6 +126,19 @@ __global__ __launch_bounds__(256) void conv4x4_bias_grad_kernel(const float *__r
 static long long dcw_chunks(int N, int H, int W, int stride) { return (long long)N * c4_out(H, stride) * ((c4_out(W, stride) + 31) / 32); }
 static int dcw_splits(int N, int Cin, int Cout, int H, int W, int stride, int splits) {
     const long long chunks = dcw_chunks(N, H, W, stride);
+    long long S = splits > 0 ? splits : slr_wgrad_auto_splits(chunks, (long long)c4_tiles(Cin) * c4_tiles(Cout), (long long)Cout * Cin * 16 * 4);
+    if (S > 65535) S = 65535;
+    return (int)(S < chunks ? S : chunks);
+}
+
+// the same for the motion encoder's convolution (stride 2, padding 1): OH = (H - 2) / 2 + 1
+static int e4_out(int H) { return (H - 2) / 2 + 1; }
+static bool e4_sizes_ok(int N, int Cin, int Cout, int H, int W) {
+    return H >= 2 && W >= 2 && c4_sizes_ok(N, Cin, Cout, H, W, 2);
+}
+static long long ecw_chunks(int N, int H, int W) { return (long long)N * e4_out(H) * ((e4_out(W) + 31) / 32); }
+static int ecw_splits(int N, int Cin, int Cout, int H, int W, int splits) {
+    const long long chunks = ecw_chunks(N, H, W);
     long long S = splits > 0 ? splits : slr_wgrad_auto_splits(chunks, (long long)c4_tiles(Cin) * c4_tiles(Cout), (long long)Cout * Cin * 16 * 4);
     if (S > 65535) S = 65535;
     return (int)(S < chunks ? S : chunks);
@@ -232,6 +248,42 @@ SLR_EXPORT int slr_conv4x4_weight_grad(const float *x, const float *g, const flo
     SLR_CHECK_LAUNCH();
     if (db) {
         hipLaunchKernelGGL(conv4x4_bias_grad_kernel, dim3(Cout), dim3(256), 0, st, g, gate, db, N, Cout, OH * OW, slope);
+        SLR_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+SLR_EXPORT size_t slr_conv4x4s2_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int splits) {
+    if (!e4_sizes_ok(N, Cin, Cout, H, W) || splits < 0) return 0;
+    return al256((size_t)ecw_splits(N, Cin, Cout, H, W, splits) * 16 * Cout * Cin * sizeof(float));
+}
+
+SLR_EXPORT int slr_conv4x4s2_weight_grad(const float *x, const float *g, float *dw, float *db, int N, int Cin, int Cout, int H, int W,
+                                         int leaky, float slope, int splits, void *ws, size_t ws_bytes, void *stream) {
+    SLR_CHECK_ARG(x && g && dw, "null pointer");
+    SLR_CHECK_ARG(e4_sizes_ok(N, Cin, Cout, H, W), "sizes (H, W >= 2)");
+    SLR_CHECK_ARG(splits >= 0, "splits (0 = chosen by the library)");
+    SLR_CHECK_ARG(!(((uintptr_t)x | (uintptr_t)g | (uintptr_t)dw | (uintptr_t)db) & 3), "4-byte aligned tensors");
+    if (!ws || ((uintptr_t)ws & 255) || ws_bytes < slr_conv4x4s2_grad_ws_bytes(N, Cin, Cout, H, W, splits)) {
+        set_error("%s: ws: slr_conv4x4s2_grad_ws_bytes(N, Cin, Cout, H, W, splits) bytes, 256-byte aligned", __func__);
+        return SLR_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int OH = e4_out(H), OW = e4_out(W), CX = (OW + 31) / 32;
+    const int S = ecw_splits(N, Cin, Cout, H, W, splits), chunks = (int)ecw_chunks(N, H, W);
+    float *part = (float *)ws;
+    const float *none = nullptr;
+    const dim3 grid(S, c4_tiles(Cin), c4_tiles(Cout));
+    if (leaky)
+        hipLaunchKernelGGL((conv4x4_wgrad_kernel<2, 1, true>), grid, dim3(256), 0, st, x, g, none, part, N, Cin, Cout, H, W, OH, OW, chunks, CX, slope);
+    else
+        hipLaunchKernelGGL((conv4x4_wgrad_kernel<2, 1, false>), grid, dim3(256), 0, st, x, g, none, part, N, Cin, Cout, H, W, OH, OW, chunks, CX, slope);
+    SLR_CHECK_LAUNCH();
+    const long long total = (long long)Cout * Cin * 16;
+    hipLaunchKernelGGL(conv4x4_wgrad_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float *)part, dw, S, total);
+    SLR_CHECK_LAUNCH();
+    if (db) {
+        hipLaunchKernelGGL(conv4x4_bias_grad_kernel, dim3(Cout), dim3(256), 0, st, g, none, db, N, Cout, OH * OW, slope);
         SLR_CHECK_LAUNCH();
     }
     return 0;

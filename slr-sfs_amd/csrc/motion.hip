@@ -14,7 +14,8 @@ namespace slr {
 // ------------------------------------------------------------------ instance norm + SPADE modulation
 // nn.InstanceNorm2d(C) (affine=False, eps, biased variance) and out = norm(x) * (1 + gamma) + beta (networks.py:441-463); gamma / beta
 // are the two halves of gb [N, 2C, H, W] (one 3x3 convolution 128 -> 2C).  One workgroup per (n, c) plane: two passes for mean and
-// variance (fp32 partial sums, tree reduction), a third for the output.
+// variance (fp32 partial sums, tree reduction), a third for the output.  KEEP: the training forward (slr_instnorm_spade_train_forward) --
+// the same code, so the same bits, which also writes the plane's mean and rstd for the backward (csrc/motion_grad.hip).
 __device__ __forceinline__ float block_sum1024(float v, float *sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -27,8 +28,10 @@ __device__ __forceinline__ float block_sum1024(float v, float *sh) {
     return t;
 }
 
+template <bool KEEP>
 __global__ __launch_bounds__(1024) void instnorm_spade_kernel(const float *__restrict__ x, const float *__restrict__ gb,
-                                                              float *__restrict__ out, int C, int HW, float eps) {
+                                                              float *__restrict__ out, float *__restrict__ mean_out,
+                                                              float *__restrict__ rstd_out, int C, int HW, float eps) {
     __shared__ float sh[16];
     const size_t plane = blockIdx.x;
     const int n = (int)(plane / C), c = (int)(plane % C);
@@ -45,6 +48,10 @@ __global__ __launch_bounds__(1024) void instnorm_spade_kernel(const float *__res
     }
     const float var = block_sum1024(q, sh) / (float)HW;
     const float rstd = 1.0f / sqrtf(var + eps);
+    if (KEEP && threadIdx.x == 0) {
+        mean_out[plane] = mean;
+        rstd_out[plane] = rstd;
+    }
     float *op = out + plane * HW;
     for (int i = threadIdx.x; i < HW; i += 1024) op[i] = ((xp[i] - mean) * rstd) * (1.0f + g[i]) + b[i];
 }
@@ -53,7 +60,19 @@ SLR_EXPORT int slr_instnorm_spade(const float *x, const float *gamma_beta, float
                                   void *stream) {
     SLR_CHECK_ARG(x && gamma_beta && out, "null pointer");
     SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && (long long)N * C < (1LL << 31) && (long long)H * W < (1LL << 31) - 1024, "sizes");
-    hipLaunchKernelGGL(instnorm_spade_kernel, dim3((unsigned)(N * C)), dim3(1024), 0, (hipStream_t)stream, x, gamma_beta, out, C, H * W, eps);
+    hipLaunchKernelGGL(instnorm_spade_kernel<false>, dim3((unsigned)(N * C)), dim3(1024), 0, (hipStream_t)stream, x, gamma_beta, out,
+                       (float *)nullptr, (float *)nullptr, C, H * W, eps);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+SLR_EXPORT int slr_instnorm_spade_train_forward(const float *x, const float *gamma_beta, float *out, float *mean, float *rstd, int N, int C,
+                                                int H, int W, float eps, void *stream) {
+    SLR_CHECK_ARG(x && gamma_beta && out && mean && rstd, "null pointer");
+    SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && (long long)N * C < (1LL << 31) && (long long)H * W < (1LL << 31) - 1024 &&
+                  (long long)H * W >= 4, "sizes (planes of at least 2 x 2)");
+    hipLaunchKernelGGL(instnorm_spade_kernel<true>, dim3((unsigned)(N * C)), dim3(1024), 0, (hipStream_t)stream, x, gamma_beta, out, mean,
+                       rstd, C, H * W, eps);
     SLR_CHECK_LAUNCH();
     return 0;
 }
