@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 23
+#define SLR_ABI_VERSION 24
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -1037,6 +1037,53 @@ int slr_motion_loss(const float *pred, const float *gt, double *sums, int N, int
  * w_epe, w_l1: DEVICE scalars (the gradients reaching the two means), either may be NULL (that term is absent). */
 int slr_motion_loss_grad(const float *pred, const float *gt, const float *w_epe, const float *w_l1, float *gpred, int N, int H, int W,
                          void *stream);
+
+/* ------------------------------------------------------------------ the head of the two-layer model (ABI 24; csrc/layers.hip)
+ * What models/animating_softmax_splating_2layers_alpha_seperate.py computes between its networks' raw outputs and its loss dictionary.
+ * All planes contiguous NCHW fp32.  Nothing synchronises; no atomics: every sum is a per-workgroup partial sum in double, added by a
+ * second launch in a fixed order, the same bits from run to run.  Per element every operation is the fp32 one torch does, products with
+ * masks included (0 * NaN = NaN); sign(0) = sign(NaN) = 0 (torch.sign).  16-byte accesses where H W (the composite) or W (the losses) is
+ * a multiple of 4 and every tensor is 16-byte aligned, scalar accesses elsewhere. */
+
+/* fluid_raw, bg_raw [N,3,H,W], fluid_alpha_raw, bg_alpha_raw [N,1,H,W] ->
+ *   fluid = tanh(fluid_raw), bg = tanh(bg_raw)   (:598, :372)
+ *   af = sigmoid(fluid_alpha_raw), ab = sigmoid(bg_alpha_raw), n = max(af + ab, 1e-8)   (:608, :616-617; a NaN sum stays NaN)
+ *   pred = (af fluid + ab bg) / n  [N,3,H,W]   (:652),   composite_alpha = af / n  [N,1,H,W]   (:775, :789). */
+int slr_layer_composite_forward(const float *fluid_raw, const float *bg_raw, const float *fluid_alpha_raw, const float *bg_alpha_raw,
+                                float *pred, float *fluid, float *bg, float *composite_alpha, int N, int H, int W, void *stream);
+
+/* The four input gradients in one pass from g_pred, g_fluid, g_bg [N,3,H,W], the gradients reaching pred, fluid and bg (each may be NULL:
+ * absent).  The chain is autograd's: the gradient reaching n passes on to af and ab only where af + ab >= 1e-8 (where the clamp bites,
+ * nothing flows through n).  Each output may be NULL (not wanted), not all four. */
+int slr_layer_composite_backward(const float *fluid_raw, const float *bg_raw, const float *fluid_alpha_raw, const float *bg_alpha_raw,
+                                 const float *g_pred, const float *g_fluid, const float *g_bg, float *d_fluid_raw, float *d_bg_raw,
+                                 float *d_fluid_alpha_raw, float *d_bg_alpha_raw, int N, int H, int W, void *stream);
+
+/* Workspace of slr_alpha_losses_forward in bytes (8-byte aligned, else SLR_E_WORKSPACE); 0 for sizes it refuses (H or W < 2). */
+size_t slr_alpha_losses_ws_bytes(int N, int H, int W);
+
+/* a_start [N,2,H,W] (channel 0 the background logit a0, channel 1 the fluid logit a1); mask_rock r, small_motion_alpha, warped_alpha,
+ * norm, fluid_alpha_raw f [N,1,H,W].  With m = 1 - small_motion_alpha, sf = sigmoid(a1), sb = sigmoid(a0):
+ *   c0 = sf / max(sf + sb, 1e-8)   (:420-421),   gt_alpha = 0.25 r m + (1 - r) m + 0.5 small_motion_alpha   (:619-621),   both [N,1,H,W]
+ *   err = (c0 m - gt_alpha m)^2
+ *   losses[0]  AlphaMSEloss: reweight != 0:  0.5 (sum r m err / (1 + sum r m) + sum (1 - r) m err / (1 + sum (1 - r) m))   (:660-666)
+ *                            reweight == 0:  mean err   (:694-697)
+ *   losses[1]  AlphaTV = TV(a1) + TV(sb), TV(x) = mean |x[..., :-1] - x[..., 1:]| + mean |x[..., :-1, :] - x[..., 1:, :]|   (:67-71, :728:
+ *              the fluid plane as the raw logit, the background plane after its sigmoid)
+ *   losses[2]  Alpha Decoder Consistency Loss = mean S(warped_alpha k - f k), k = norm > 1e-8, S(d) = |d| + 0.1 (2 sigmoid(5 |d|) - 1)
+ *              (:63-65, :758-759)
+ *   losses[3]  its moving-region form, mean S(.) m   (:763-764)
+ *   losses[4], [5]  0.5 / (1 + sum r m) and 0.5 / (1 + sum (1 - r) m), which the backward reads;  losses[6], [7] = 0.
+ * losses: 8 floats in device memory.  H, W >= 2. */
+int slr_alpha_losses_forward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *warped_alpha,
+                             const float *norm, const float *fluid_alpha_raw, float *losses, float *gt_alpha, float *c0, int reweight,
+                             int N, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* d_a_start [N,2,H,W] and d_fluid_alpha_raw [N,1,H,W] (either may be NULL) from g_losses [4], the gradients reaching losses[0 .. 3]
+ * (device), and `losses`, the forward's vector.  The TV term is a five-point stencil; warped_alpha receives no gradient. */
+int slr_alpha_losses_backward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *warped_alpha,
+                              const float *norm, const float *fluid_alpha_raw, const float *losses, const float *g_losses,
+                              float *d_a_start, float *d_fluid_alpha_raw, int reweight, int N, int H, int W, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 23
+ABI_VERSION = 24
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -142,6 +142,11 @@ SIGNATURES = {
     "slr_motion_loss_ws_bytes": (_sz, [_i, _i, _i]),
     "slr_motion_loss": (_i, [_fp, _fp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "slr_motion_loss_grad": (_i, [_fp] * 5 + [_i, _i, _i, _vp]),
+    "slr_layer_composite_forward": (_i, [_fp] * 8 + [_i, _i, _i, _vp]),
+    "slr_layer_composite_backward": (_i, [_fp] * 11 + [_i, _i, _i, _vp]),
+    "slr_alpha_losses_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_alpha_losses_forward": (_i, [_fp] * 9 + [_i, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_alpha_losses_backward": (_i, [_fp] * 10 + [_i, _i, _i, _i, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

@@ -1,0 +1,378 @@
+"""The head of the reference's two-layer model (``AnimatingSoftmaxSplatingJoint``, models/animating_softmax_splating_2layers_alpha_seperate.py)
+on csrc/layers.hip (ABI 24): what lies between the networks' raw outputs and the loss dictionary.
+
+``layer_composite``   tanh / sigmoid of the raw outputs and the alpha-normalised composite of the fluid and the background layer
+                      (:372, :598, :608, :616-617, :652, :775-789).
+``alpha_losses``      the (reweighted) alpha MSE against the rock mask, the alpha total variation and the two alpha-decoder consistency
+                      losses (:420-421, :619-621, :658-666, :694-699, :727-729, :757-765).
+
+``TwoLayerTrainingModel``  the model: ``AnimatingSoftmaxSplatingJoint.forward(batch)`` for the options of
+                      train_alpha_finetuneBG_finetuneFluid_v2.sh, with the reference's checkpoint keys; ``Trainer`` takes it as it is.
+
+Both operators are one ``torch.autograd.Function``: a forward and a backward of one or two launches each instead of about forty
+elementwise and reduction launches forward and twice that backward.  Device tensors only: CPU tensors raise, there is no fallback.
+Nothing here synchronises the host; there are no atomics, results have the same bits from run to run."""
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from . import spectral as _spectral
+from .losses import VGG19_CONVS, SynthesisLoss, load_vgg19_state_dict
+from .model import TrainingModel, _in_reference_order, _vgg_key, check_options
+from .optim import _value
+from .trainable import TrainableBGDecoder, TrainableDecoderPconv2, TrainableEncoder, TrainableEncoderWithZ
+from .training import TrainingSynthesis, _flag, splat_blend
+
+LOSS_NAMES = ("AlphaMSEloss", "AlphaTV", "Alpha Decoder Consistency Loss", "Moving Region Alpha Decoder Consistency Loss")
+
+
+def _check_planes(what, planes, min_hw):
+    """``planes``: (name, tensor, channels), all [N,channels,H,W] float32, contiguous, on one device -- checked before the device is
+    touched, in the order of ``training._check_inputs``.  Returns (N, H, W)."""
+    for name, t, _ in planes:
+        if not torch.is_tensor(t):
+            raise TypeError(f"slr_sfs_amd.layers.{what}: tensors required, got {type(t).__name__} for {name}")
+    for _, t, _ in planes:                               # (the reference raises NotImplementedError for CPU tensors, softsplat.py:418-419)
+        if not t.is_cuda:
+            raise NotImplementedError("slr_sfs_amd.layers run on ROCm device tensors only (no CPU path)")
+    for name, t, _ in planes:
+        if t.dtype != torch.float32:
+            raise TypeError(f"slr_sfs_amd.layers.{what}: float32 tensors required, got {t.dtype} for {name}")
+    name0, first, c0 = planes[0]
+    if first.dim() != 4 or min(first.shape) < 1:
+        raise ValueError(f"{what}: {name0} [N,{c0},H,W] with N, H, W >= 1 required, got {tuple(first.shape)}")
+    N, _, H, W = first.shape
+    for name, t, c in planes:
+        if tuple(t.shape) != (N, c, H, W):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)}, expected {(N, c, H, W)}")
+        if t.device != first.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, {name0} on {first.device}")
+    if H < min_hw or W < min_hw:
+        raise ValueError(f"{what}: H, W >= {min_hw} required (the total variation is a mean over nothing below), got {H} x {W}")
+    for name, t, _ in planes:
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} is not contiguous")
+    return N, H, W
+
+
+def _grad_or_none(g, like):
+    """An incoming gradient as the kernels take it: None when autograd has none for that output."""
+    if g is None:
+        return None
+    g = g.contiguous()
+    _lib.require_device(g)
+    assert g.shape == like.shape
+    return g
+
+
+# ---------------------------------------------------------------------------------------------- the composite
+
+class _LayerComposite(torch.autograd.Function):
+    """forward(fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw) -> (pred, fluid, bg, composite_alpha); saved: the four inputs (the
+    backward recomputes tanh and sigmoid: two transcendental functions a pixel cost less than reading three more planes)."""
+
+    @staticmethod
+    def forward(ctx, fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw):
+        N, _, H, W = fluid_raw.shape
+        pred, fluid, bg = torch.empty_like(fluid_raw), torch.empty_like(fluid_raw), torch.empty_like(fluid_raw)
+        ca = torch.empty_like(fluid_alpha_raw)
+        _lib.call("slr_layer_composite_forward", fluid_raw.device, fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw, pred, fluid, bg, ca,
+                  N, H, W)
+        ctx.save_for_backward(fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw)
+        ctx.mark_non_differentiable(ca)
+        ctx.set_materialize_grads(False)                 # an output nobody differentiates arrives as None, not as a plane of zeros
+        return pred, fluid, bg, ca
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pred, g_fluid, g_bg, _g_ca):
+        need = ctx.needs_input_grad[:4]
+        if not any(need):
+            return None, None, None, None
+        fluid_raw, bg_raw, fa, ba = ctx.saved_tensors
+        N, _, H, W = fluid_raw.shape
+        g_pred, g_fluid, g_bg = (_grad_or_none(g, fluid_raw) for g in (g_pred, g_fluid, g_bg))
+        outs = [torch.empty_like(t) if n else None for t, n in zip((fluid_raw, bg_raw, fa, ba), need)]
+        _lib.call("slr_layer_composite_backward", fluid_raw.device, fluid_raw, bg_raw, fa, ba, g_pred, g_fluid, g_bg, *outs, N, H, W)
+        return tuple(outs)
+
+
+def layer_composite(fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw):
+    """(pred, fluid, bg, composite_alpha) of the raw outputs of the projector and ``net_bg`` [N,3,H,W] and of the alpha decoder and the
+    alpha encoder's background channel [N,1,H,W]:
+
+        fluid = tanh(fluid_raw), bg = tanh(bg_raw), af = sigmoid(fluid_alpha_raw), ab = sigmoid(bg_alpha_raw), n = max(af + ab, 1e-8)
+        pred = (af fluid + ab bg) / n,   composite_alpha = af / n   (no gradient: it is only shown)
+
+    differentiable in all four inputs through ``pred``, ``fluid`` and ``bg``; where the clamp bites, nothing flows through ``n``."""
+    _check_planes("layer_composite", (("fluid_raw", fluid_raw, 3), ("bg_raw", bg_raw, 3), ("fluid_alpha_raw", fluid_alpha_raw, 1),
+                                      ("bg_alpha_raw", bg_alpha_raw, 1)), 1)
+    return _LayerComposite.apply(fluid_raw, bg_raw, fluid_alpha_raw, bg_alpha_raw)
+
+
+# ---------------------------------------------------------------------------------------------- the alpha losses
+
+class _AlphaLosses(torch.autograd.Function):
+    """forward(a_start, mask_rock, small_motion_alpha, warped_alpha, norm, fluid_alpha_raw, reweight) -> (values [8], GTAlpha, c0): the
+    kernel's vector, the four losses and the two reweighting factors the backward reads; saved: the inputs and that vector."""
+
+    @staticmethod
+    def forward(ctx, a_start, mask_rock, sma, warped, norm, fluid_alpha_raw, reweight):
+        N, _, H, W = a_start.shape
+        dev = a_start.device
+        vec = a_start.new_empty(8)
+        gt, c0 = torch.empty_like(mask_rock), torch.empty_like(mask_rock)
+        ws = torch.empty(_lib.lib().slr_alpha_losses_ws_bytes(N, H, W), dtype=torch.uint8, device=dev)
+        _lib.call("slr_alpha_losses_forward", dev, a_start, mask_rock, sma, warped, norm, fluid_alpha_raw, vec, gt, c0, int(reweight),
+                  N, H, W, ws, ws.numel())
+        ctx.save_for_backward(a_start, mask_rock, sma, warped, norm, fluid_alpha_raw, vec)
+        ctx.reweight = int(reweight)
+        ctx.mark_non_differentiable(gt, c0)
+        return vec, gt, c0
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_vals, _g_gt, _g_c0):
+        need_a, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[5]
+        if not (need_a or need_f):
+            return (None,) * 7
+        a_start, mask_rock, sma, warped, norm, far, vec = ctx.saved_tensors
+        N, _, H, W = a_start.shape
+        g_vals = g_vals.contiguous()
+        _lib.require_device(g_vals)
+        da = torch.empty_like(a_start) if need_a else None
+        df = torch.empty_like(far) if need_f else None
+        _lib.call("slr_alpha_losses_backward", a_start.device, a_start, mask_rock, sma, warped, norm, far, vec, g_vals, da, df,
+                  ctx.reweight, N, H, W)
+        return da, None, None, None, None, df, None
+
+
+def alpha_losses(a_start, mask_rock, small_motion_alpha, warped_alpha, norm, fluid_alpha_raw, *, reweight=True):
+    """(losses, GTAlpha, c0): the alpha terms of the two-layer model's loss dictionary, each a 0-dim tensor under the reference's key
+    (``LOSS_NAMES``), and the planes GTAlpha and c0 = CompositeFluidAlpha_I0 [N,1,H,W] (no gradient).
+
+    ``a_start`` [N,2,H,W]: the alpha encoder's output on the start image (channel 0 the background logit, channel 1 the fluid logit);
+    ``mask_rock``, ``small_motion_alpha``, ``warped_alpha`` (the splatted, normalised alpha plane: it receives no gradient), ``norm`` (the
+    splat's normaliser) and ``fluid_alpha_raw`` (the alpha decoder's output) [N,1,H,W].  ``reweight``: ``use_reweight_mask_loss``.
+    Differentiable in ``a_start`` and ``fluid_alpha_raw``.  H, W >= 2: the reference's total variation is a mean over nothing below."""
+    _check_planes("alpha_losses", (("a_start", a_start, 2), ("mask_rock", mask_rock, 1), ("small_motion_alpha", small_motion_alpha, 1),
+                                   ("warped_alpha", warped_alpha, 1), ("norm", norm, 1), ("fluid_alpha_raw", fluid_alpha_raw, 1)), 2)
+    vals, gt, c0 = _AlphaLosses.apply(a_start, mask_rock.detach(), small_motion_alpha.detach(), warped_alpha.detach(), norm.detach(),
+                                      fluid_alpha_raw, bool(reweight))
+    return {name: vals[k] for k, name in enumerate(LOSS_NAMES)}, gt, c0
+
+
+# ---------------------------------------------------------------------------------------------- the model
+
+ALPHA_REFINE_MODEL_TYPE = "resnet_256W8UpDown64Layers_de_resnet_pconv2_nonorm"
+BG_REFINE_MODEL_TYPE = "resnet_256W8UpDown64BG_nonorm"
+# flags of the reference's forward() outside train_alpha_finetuneBG_finetuneFluid_v2.sh; use_alpha0_as_blending_weight (the v1 script: a
+# second weight group in the splat) is the next one to build
+_REFUSED_FLAGS = ("use_alpha0_as_blending_weight", "use_alpha_tau", "use_sum1_alpha", "use_reweight_mask_loss2", "use_static_moving_loss",
+                  "use_fluid_img_at_static_region", "use_start_img_at_static_region", "use_gt_mean_img", "use_input_img",
+                  "use_fluid_alpha_only", "use_bg_alpha_only", "use_motion_as_alpha_input", "use_mask_as_alpha_input",
+                  "use_bg_as_alpha_input", "train_inpaint", "augmented_edge_mask", "use_MotionMaskThreshold", "use_start_img_only")
+_REFUSED_POSITIVE = ("use_alpha_softmax", "clamp_alpha", "AKLloss", "AlphaL1loss", "RockRegionloss", "FluidRegionloss")
+_NETS = ("encoder", "net_bg", "net_alpha_encoder", "net_alpha_decoder", "projector")      # the reference's registration order
+NOISE_KEYS = ("start_dropped", "end_dropped", "start", "end", "bg", "alpha_start", "alpha_end", "projector", "alpha_decoder")
+
+
+def _refuse2(name, why=""):
+    raise NotImplementedError(f"slr_sfs_amd.TwoLayerTrainingModel: option {name} is not implemented{why}")
+
+
+def check_two_layer_options(opts):
+    """Everything ``model.check_options`` refuses, and every path of the two-layer forward() that
+    train_alpha_finetuneBG_finetuneFluid_v2.sh does not take: NotImplementedError naming the flag."""
+    check_options(opts)
+    for name in _REFUSED_FLAGS:
+        if _flag(opts, name):
+            _refuse2(name, " (the next one to build: a second weight group in splat_blend)" if name == "use_alpha0_as_blending_weight" else "")
+    for name in _REFUSED_POSITIVE:
+        if float(_value(opts, name, 0.0) or 0.0) > 0.0:
+            _refuse2(f"{name}={_value(opts, name, 0.0)}")
+    alpha_type = str(_value(opts, "alpha_refine_model_type", ALPHA_REFINE_MODEL_TYPE))
+    for part in ("decouple", "image"):
+        if part in alpha_type:
+            _refuse2(f"alpha_refine_model_type={alpha_type} ({part})")
+    if alpha_type != ALPHA_REFINE_MODEL_TYPE:
+        _refuse2(f"alpha_refine_model_type={alpha_type}", f" (only {ALPHA_REFINE_MODEL_TYPE})")
+    if str(_value(opts, "bg_refine_model_type", BG_REFINE_MODEL_TYPE)) != BG_REFINE_MODEL_TYPE:
+        _refuse2(f"bg_refine_model_type={_value(opts, 'bg_refine_model_type', None)}", f" (only {BG_REFINE_MODEL_TYPE})")
+    for name in ("train_bg", "train_alpha"):             # (without them the reference builds no such network and its forward fails)
+        if not _flag(opts, name):
+            _refuse2(f"{name}=False")
+
+
+class TwoLayerTrainingModel(TrainingModel):
+    """``AnimatingSoftmaxSplatingJoint`` (models/animating_softmax_splating_2layers_alpha_seperate.py:130-190, forward :256-809) for
+    training, under the options of train_alpha_finetuneBG_finetuneFluid_v2.sh.  forward(batch) -> (loss_dict, pred_dict), the reference's
+    line by line, with its keys.
+
+    batch: ``images`` [start, middle, end], ``motions`` and ``index`` as ``TrainingModel`` takes them; ``mean_video``: a list whose first
+    entry is the mean frame [B,3,W,W]; ``mask_rock`` [B,1,W,W]; optional ``noise``: a dict with the (noise1, noise2) pairs of every block
+    per network call, under ``NOISE_KEYS``.  The loss weights AlphaMSEloss, ATVloss, ADCloss, MRADCloss, MVloss are read from ``opts`` at
+    EACH forward (the training script decays AlphaMSEloss every epoch); a weight of 0 skips the term, as there.
+
+    The reference calls its encoder on the start and the end image twice (:349-350, :359-360) and drops the first pair; in train() mode
+    those calls still advance weight_u / weight_v and the batch-norm statistics and draw noise.  ``literal_encoder_calls`` (default) makes
+    them too, under no_grad, so that the buffers after a forward are the reference's; False skips them.
+    widths / updown keywords: other widths than the reference's (tests).  ``deterministic``: as ``TrainingModel``."""
+
+    def __init__(self, opts, vgg=None, *, encoder_widths=None, decoder_widths=None, decoder_updown=None, alpha_encoder_widths=None,
+                 alpha_decoder_widths=None, alpha_decoder_updown=None, bg_widths=None, bg_updown=None, deterministic=False,
+                 literal_encoder_calls=True):
+        nn.Module.__init__(self)
+        check_two_layer_options(opts)
+        self.opt = opts
+        self.literal_encoder_calls = bool(literal_encoder_calls)
+        ngf = self.ngf = int(_value(opts, "ngf", 64))
+        self.encoder = TrainableEncoderWithZ(cin=3, feat=ngf, widths=encoder_widths, spectral=True)
+        self.synthesis = TrainingSynthesis(opts, deterministic=deterministic)      # (its options and Euler integration; the splat is called here)
+        self.synthesis.options["clamp_z"] = None if _flag(opts, "no_clamp_Z") else (-20.0, 20.0)      # :476: by value in this model
+        self.net_bg = TrainableBGDecoder(cin=3, cout=3, widths=bg_widths, updown=bg_updown, spectral=True)
+        self.net_alpha_encoder = TrainableEncoder(cin=3, cout=2, widths=alpha_encoder_widths, spectral=True)
+        self.net_alpha_decoder = TrainableDecoderPconv2(cin=ngf + 1, cout=1, widths=alpha_decoder_widths, updown=alpha_decoder_updown,
+                                                        spectral=True)
+        self.projector = TrainableDecoderPconv2(cin=ngf, cout=3, widths=decoder_widths, updown=decoder_updown, spectral=True)
+        self.loss_function = SynthesisLoss(opts, vgg)
+        self.register_buffer("min_z", torch.Tensor([0.1]))                                        # :183-190, literally
+        self.register_buffer("max_z", torch.Tensor([_value(opts, "max_z", 10.0)]))
+        self.register_buffer("discretized_zs", torch.linspace(_value(opts, "min_z", 0.5), _value(opts, "max_z", 10.0),
+                                                              int(_value(opts, "voxel_size", 64))))
+        self.defer_weight_grad(True)
+
+    def defer_weight_grad(self, on=True):
+        for name in _NETS:
+            _spectral.defer_weight_grad(getattr(self, name), on)
+        return self
+
+    def _weight(self, name):
+        return float(_value(self.opt, name, 0.0) or 0.0)
+
+    def _planes(self, batch, start):
+        """mean_video[0] and mask_rock of the batch, checked like the images."""
+        mean = batch["mean_video"]
+        if not isinstance(mean, (list, tuple)) or not len(mean):
+            raise ValueError("TwoLayerTrainingModel: batch['mean_video'] is a list whose first entry is the mean frame")
+        out = []
+        for name, t, c in (("mean_video[0]", mean[0], 3), ("mask_rock", batch["mask_rock"], 1)):
+            if not torch.is_tensor(t):
+                raise TypeError(f"TwoLayerTrainingModel: {name}: a tensor is required, got {type(t).__name__}")
+            if not t.is_cuda:
+                raise NotImplementedError("slr_sfs_amd operators run on ROCm device tensors only (no CPU path)")
+            if tuple(t.shape) != (start.shape[0], c, start.shape[2], start.shape[3]):
+                raise ValueError(f"TwoLayerTrainingModel: {name} {tuple(t.shape)}, expected {(start.shape[0], c, *start.shape[2:])}")
+            out.append(t.float().contiguous())                                                      # :343: mask_rock.float()
+        return out
+
+    def forward(self, batch):
+        (start_img, middle_img, end_img), motions, (start_index, middle_index, end_index), bs, W = self._batch(batch)
+        mean_img, mask_rock = self._planes(batch, start_img)
+        noise = batch.get("noise") or {}
+        if motions.shape[1] == 2:                                                                 # :324-332
+            flow = motions
+        else:
+            flow = motions[:, :2, ...].clone()
+            flow = flow * motions[:, 2:3, ...]
+        flow = flow.reshape(bs, 2, W, W).contiguous()
+        with torch.no_grad():                                                                     # :334-342: a few torch lines, no gradient
+            motion_speed = (flow[:, 0:1] ** 2 + flow[:, 1:2] ** 2).sqrt()
+            small_motion_alpha = (motion_speed < motion_speed.mean([1, 2, 3], True) * 0.1).float()
+            # (label, :343-344, is computed there and never used)
+        if self.literal_encoder_calls:                                                            # :349-350: run and dropped
+            with torch.no_grad():
+                self.encoder(start_img, noise=noise.get("start_dropped"))
+                self.encoder(end_img, noise=noise.get("end_dropped"))
+        start_fs, Z_f = self.encoder(start_img, noise=noise.get("start"))                         # :359-366
+        end_fs, Z_p = self.encoder(end_img, noise=noise.get("end"))
+        bg_raw = self.net_bg(start_img, noise=noise.get("bg"))                                    # :369
+        a_start = self.net_alpha_encoder(start_img, noise=noise.get("alpha_start"))               # :387
+        a_end = self.net_alpha_encoder(end_img, noise=noise.get("alpha_end"))                     # :400
+        dev = start_fs.device
+        start_index, middle_index, end_index = (torch.as_tensor(v, device=dev) for v in (start_index, middle_index, end_index))
+        euler = self.synthesis.euler_integration
+        flow_f = euler(flow, middle_index.long() - start_index.long())                            # :454
+        flow_p = euler(-flow, end_index.long() + 1 - middle_index.long())                         # :455
+        alpha = (1.0 - (middle_index.float() - start_index.float()).float() / (
+            end_index.float() - start_index.float() + 1).float()).reshape(bs)                     # :459-460
+        alpha = torch.clamp(alpha, min=1.0 / 600.0, max=599.0 / 600.0).contiguous()               # :461: this model only
+        o = self.synthesis.options
+        if not o["train_z"]:
+            Z_f = Z_p = None
+        # :488-490, :542-543, :565-576: the alpha logit plane is splatted with the features' own weights -- channel ngf of one splat
+        splat, norm = splat_blend(torch.cat([start_fs, a_start[:, 1:2]], 1), Z_f, flow_f, torch.cat([end_fs, a_end[:, 1:2]], 1), Z_p,
+                                  flow_p, alpha, clamp_z=o["clamp_z"], subtract_max=o["subtract_max"], return_norm=True,
+                                  **({"deterministic": True} if self.synthesis.deterministic else {}))
+        gen_fs = splat[:, :self.ngf].contiguous()
+        fluid_raw = self.projector(gen_fs, noise=noise.get("projector"))                          # :597
+        fluid_alpha_raw = self.net_alpha_decoder(splat, noise=noise.get("alpha_decoder"))         # :606: cat([gen_fs, alpha_fluid], 1)
+        gen_img, gen_fluid_img, gen_bg_img_f, composite_alpha = layer_composite(fluid_raw, bg_raw, fluid_alpha_raw,
+                                                                                a_start[:, 0:1].contiguous())
+        loss = self.loss_function(gen_img, middle_img)                                            # :655
+        terms, gt_alpha, _ = alpha_losses(a_start, mask_rock, small_motion_alpha, splat[:, self.ngf:].detach().contiguous(),
+                                          norm.detach().contiguous(), fluid_alpha_raw, reweight=_flag(self.opt, "use_reweight_mask_loss"))
+        for weight, name in (("AlphaMSEloss", LOSS_NAMES[0]), ("ATVloss", LOSS_NAMES[1])):        # :658-699, :727-729
+            if self._weight(weight) > 0.0:
+                loss[name] = terms[name]
+                loss["Total Loss"] = loss["Total Loss"] + loss[name] * self._weight(weight)
+        if self._weight("MVloss") > 0.0:                                                          # :731-739
+            loss_bgimg = self.loss_function(gen_bg_img_f, mean_img)
+            for loss_name in loss_bgimg:
+                if "Perceptual" in loss_name or "L1" in loss_name:
+                    loss[loss_name + "_bg"] = loss_bgimg[loss_name]
+                elif "Total" in loss_name:
+                    loss[loss_name] = loss[loss_name] + loss_bgimg[loss_name] * self._weight("MVloss")
+        for weight, name in (("ADCloss", LOSS_NAMES[2]), ("MRADCloss", LOSS_NAMES[3])):           # :757-765
+            if self._weight(weight) > 0.0:
+                loss[name] = terms[name]
+                loss["Total Loss"] = loss["Total Loss"] + loss[name] * self._weight(weight)
+        with torch.no_grad():                                                                     # (shown, not differentiated)
+            shown = torch.sigmoid(a_start)
+        pred_dict = {"OutputImg": middle_img, "PredImg": gen_img, "BGImg_f": gen_bg_img_f, "MeanImg": mean_img, "FluidImg": gen_fluid_img,
+                     "AlphaFluid_f": shown[:, 1:2], "AlphaBG_f": shown[:, 0:1], "CompositeFluidAlpha": composite_alpha,
+                     "Z_f": self._z_f_norm(Z_f, start_fs), "GTMotion": flow, "GTAlpha": gt_alpha, "RockMask": mask_rock}     # :777-796
+        return loss, pred_dict
+
+    # ---- the reference's state dict
+    def _reference_entries(self):
+        out = {}
+        for name in _NETS:
+            out.update({name + "." + k: t for k, t in _spectral._entries(getattr(self, name)).items()})
+        i, vgg = self._vgg()
+        if vgg is not None:
+            for conv, idx in zip(vgg.convs, VGG19_CONVS):
+                out[f"loss_function.losses.{i}.model.{_vgg_key(idx)}.weight"] = conv.weight
+                out[f"loss_function.losses.{i}.model.{_vgg_key(idx)}.bias"] = conv.bias
+        for name in ("min_z", "max_z", "discretized_zs"):
+            out[name] = getattr(self, name)
+        return out
+
+    def reference_parameters(self):
+        """[(reference key, tensor, learns)] in the order of the reference model's ``parameters()``: encoder, net_bg, net_alpha_encoder,
+        net_alpha_decoder, projector, the VGG19."""
+        out = [("encoder." + k, t, l) for k, t, l in _in_reference_order(self.encoder, True)]
+        out += [("net_bg.eblocks." + k[len("gblocks."):], t, l) for k, t, l in _in_reference_order(self.net_bg, True)]     # ResNet_Blocks under eblocks
+        out += [("net_alpha_encoder." + k, t, l) for k, t, l in _in_reference_order(self.net_alpha_encoder, True)]
+        out += [("net_alpha_decoder." + k, t, l) for k, t, l in _in_reference_order(self.net_alpha_decoder, False)]
+        out += [("projector." + k, t, l) for k, t, l in _in_reference_order(self.projector, False)]
+        i, vgg = self._vgg()
+        if vgg is not None:
+            for conv, idx in zip(vgg.convs, VGG19_CONVS):
+                out += [(f"loss_function.losses.{i}.model.{_vgg_key(idx)}.weight", conv.weight, False),
+                        (f"loss_function.losses.{i}.model.{_vgg_key(idx)}.bias", conv.bias, False)]
+        return out
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix="model.module."):
+        theirs = self.check_reference_state_dict(sd, prefix)
+        for name in _NETS:
+            _spectral.load_spectral_state_dict(getattr(self, name), sd, prefix + name + ".")
+        i, vgg = self._vgg()
+        if vgg is not None:
+            head = f"loss_function.losses.{i}.model."
+            load_vgg19_state_dict(vgg, {"features." + k[len(head):].split(".", 1)[1]: v for k, v in theirs.items() if k.startswith(head)})
+        for name in ("min_z", "max_z", "discretized_zs"):
+            getattr(self, name).copy_(theirs[name])
+        return self
