@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 24
+#define SLR_ABI_VERSION 25
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -1084,6 +1084,29 @@ int slr_alpha_losses_forward(const float *a_start, const float *mask_rock, const
 int slr_alpha_losses_backward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *warped_alpha,
                               const float *norm, const float *fluid_alpha_raw, const float *losses, const float *g_losses,
                               float *d_a_start, float *d_fluid_alpha_raw, int reweight, int N, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------ the alpha-0 blending weight (ABI 25; csrc/layers.hip)
+ * train_alpha_finetuneBG_finetuneFluid_v1.sh (--use_alpha0_as_blending_weight): the alpha logit plane is splatted under exp(c0), c0 the
+ * composite fluid alpha of the START image, so c0 carries a gradient; and two more loss terms on c0 (:741-755).  Conventions as above;
+ * 16-byte accesses where H W is a multiple of 4 and every tensor is 16-byte aligned. */
+
+/* Workspace of slr_blend_alpha0_forward in bytes (8-byte aligned, else SLR_E_WORKSPACE); 0 for sizes it refuses. */
+size_t slr_blend_alpha0_ws_bytes(int N, int H, int W);
+
+/* a_start [N,2,H,W] (channel 0 the background logit a0, channel 1 the fluid logit a1); mask_rock r, small_motion_alpha [N,1,H,W].
+ * With m = 1 - small_motion_alpha, sf = sigmoid(a1), sb = sigmoid(a0), S(d) = |d| + 0.1 (2 sigmoid(5 |d|) - 1)   (:63-65):
+ *   c0 = sf / max(sf + sb, 1e-8)  [N,1,H,W]   (:420-421)
+ *   values[0]  FluidRegionLoss = mean S(c0 (1 - r) m - (1 - r) m)   (:742-744)
+ *   values[1]  RockRegionLoss  = mean S(c0 r m - rock_target r m)   (:750-753)
+ * values: 2 floats in device memory.  N, H, W >= 1. */
+int slr_blend_alpha0_forward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, float *c0, float *values,
+                             float rock_target, int N, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* d_a_start [N,2,H,W] in one pass from g_c0 [N,1,H,W], the gradient reaching c0, and g_values [2], the gradients reaching the two losses
+ * (device); either may be NULL (absent), not both.  The sigmoids are recomputed.  The chain is autograd's: where sf + sb < 1e-8 nothing
+ * flows through the clamped sum (the convention of slr_layer_composite_backward). */
+int slr_blend_alpha0_backward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *g_c0,
+                              const float *g_values, float *d_a_start, float rock_target, int N, int H, int W, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 24
+ABI_VERSION = 25
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -147,6 +147,9 @@ SIGNATURES = {
     "slr_alpha_losses_ws_bytes": (_sz, [_i, _i, _i]),
     "slr_alpha_losses_forward": (_i, [_fp] * 9 + [_i, _i, _i, _i, _vp, _sz, _vp]),
     "slr_alpha_losses_backward": (_i, [_fp] * 10 + [_i, _i, _i, _i, _vp]),
+    "slr_blend_alpha0_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_blend_alpha0_forward": (_i, [_fp] * 5 + [_f, _i, _i, _i, _vp, _sz, _vp]),
+    "slr_blend_alpha0_backward": (_i, [_fp] * 6 + [_f, _i, _i, _i, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

@@ -2,12 +2,14 @@
 // the networks' raw outputs and the loss dictionary.
 //   * the composite of the fluid and the background layer under their alphas (:372, :598, :608, :616-617, :652, :775-789) and its backward,
 //   * the alpha losses (:420-421, :619-621, :658-666, :694-699, :727-729, :757-765): the (reweighted) alpha MSE against the rock mask, the
-//     alpha total variation, the two alpha-decoder consistency losses, and their backward -- the TV as a five-point stencil.
+//     alpha total variation, the two alpha-decoder consistency losses, and their backward -- the TV as a five-point stencil,
+//   * (ABI 25) the alpha-0 blending weight of train_alpha_finetuneBG_finetuneFluid_v1.sh: c0 with a gradient, and the two region losses
+//     on it (:741-755), and their backward.
 // All planes contiguous NCHW fp32.  Nothing here synchronises; there are no atomics: sums are per-workgroup partial sums in double
 // (slr_reduce.hpp), added by a second launch in a fixed order, so every result has the same bits from run to run.  Every operation on an
 // element is the fp32 one torch would do, products with masks included (0 * NaN = NaN); sign(0) = sign(NaN) = 0 (torch.sign).
 // A thread owns four consecutive pixels of the flattened [N, H W] index: 16-byte accesses where four pixels never straddle a plane or a
-// row and the planes start aligned (H W % 4 == 0 for the composite, W % 4 == 0 for the losses), scalar accesses elsewhere.
+// row and the planes start aligned (H W % 4 == 0 for the composite and the blending weight, W % 4 == 0 for the losses), scalar accesses elsewhere.
 #include "slr_common.hpp"
 #include "slr_reduce.hpp"
 
@@ -373,6 +375,112 @@ __global__ __launch_bounds__(LY_THREADS) void alpha_losses_backward_kernel(const
     }
 }
 
+// ------------------------------------------------------------------ the alpha-0 blending weight (ABI 25)
+// c0 = sf / max(sf + sb, 1e-8) of the START image (:420-421) as the plane train_alpha_finetuneBG_finetuneFluid_v1.sh splats the alpha logit
+// with (:483-484, :538-539), and the two region losses on it (:741-755), S the file's SmoothL1Loss:
+//   Fluid = mean S(c0 (1 - r) m - (1 - r) m),   Rock = mean S(c0 r m - target r m),   m = 1 - small_motion_alpha.
+// Products in torch's order, left to right.  Partial sums, part[block * 2 + k]: 0 the fluid term, 1 the rock term.
+constexpr int B0_SUMS = 2;
+
+__global__ __launch_bounds__(LY_THREADS) void blend_alpha0_forward_kernel(const float *__restrict__ a, const float *__restrict__ rock,
+                                                                          const float *__restrict__ sma, float *__restrict__ c0_out,
+                                                                          double *__restrict__ part, float target, long long total,
+                                                                          long long HW, int vec_ok) {
+    __shared__ double red[B0_SUMS][LY_THREADS / 64];
+    double v[B0_SUMS] = {0.0, 0.0};
+    Quad q;
+    if (ly_quad(q, total, HW)) {
+        const bool vec = vec_ok && q.cnt == 4;           // (H W % 4 == 0: the four pixels lie in one sample)
+        long long o1[4], o2[4], o2b[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o1[e] = q.pix[e]; o2[e] = q.pix[e] + q.n[e] * HW; o2b[e] = o2[e] + HW; }
+        float a0[4], a1[4], r[4], sm[4], c0[4];
+        ld4(a, o2, vec, q.cnt, a0);
+        ld4(a, o2b, vec, q.cnt, a1);
+        ld4(rock, o1, vec, q.cnt, r);
+        ld4(sma, o1, vec, q.cnt, sm);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float m = 1.0f - sm[e], nr = 1.0f - r[e];
+            const float sf = ly_sigmoid(a1[e]), sb = ly_sigmoid(a0[e]);
+            c0[e] = sf / ly_clamp_eps(sf + sb);
+            const float SF = ly_smooth_l1(c0[e] * nr * m - nr * m);
+            const float SR = ly_smooth_l1(c0[e] * r[e] * m - target * r[e] * m);
+            if (e < q.cnt) { v[0] += (double)SF; v[1] += (double)SR; }
+        }
+        st4(c0_out, o1, vec, q.cnt, c0);
+    }
+    block_sum<B0_SUMS, LY_THREADS / 64>(v, red);
+    if (threadIdx.x == 0) {
+        part[(long long)blockIdx.x * B0_SUMS] = v[0];
+        part[(long long)blockIdx.x * B0_SUMS + 1] = v[1];
+    }
+}
+
+// The workgroups' partial sums in a fixed order -> out[2]: 0 FluidRegionLoss, 1 RockRegionLoss.
+__global__ __launch_bounds__(256) void blend_alpha0_finish_kernel(const double *__restrict__ part, float *__restrict__ out, int blocks,
+                                                                  double cnt) {
+    __shared__ double red[B0_SUMS][4];
+    double v[B0_SUMS] = {0.0, 0.0};
+    for (int t = threadIdx.x; t < blocks; t += 256) {
+        v[0] += part[(long long)t * B0_SUMS];
+        v[1] += part[(long long)t * B0_SUMS + 1];
+    }
+    block_sum<B0_SUMS, 4>(v, red);
+    if (threadIdx.x == 0) {
+        out[0] = (float)(v[0] / cnt);
+        out[1] = (float)(v[1] / cnt);
+    }
+}
+
+// d S(d) / d d times g: g (1 + sigmoid(5 t) (1 - sigmoid(5 t))) sign(d), t = |d|, in the operations of alpha_losses_backward_kernel.
+__device__ __forceinline__ float ly_smooth_l1_grad(float d, float g) {
+    const float sg = ly_sigmoid(5.0f * fabsf(d));
+    return (g + g * 0.2f * (1.0f - sg) * sg * 5.0f) * ly_sign(d);
+}
+
+// d a_start [N,2,H,W] from gc0 [N,1,H,W], the gradient reaching c0, and g[2], those reaching the two losses (device); either may be NULL
+// (absent).  The chain is autograd's: what reaches max(sf + sb, 1e-8) passes on only where sf + sb >= 1e-8.
+__global__ __launch_bounds__(LY_THREADS) void blend_alpha0_backward_kernel(const float *__restrict__ a, const float *__restrict__ rock,
+                                                                           const float *__restrict__ sma, const float *__restrict__ gc0,
+                                                                           const float *__restrict__ g, float *__restrict__ da,
+                                                                           float target, float inv_cnt, long long total, long long HW,
+                                                                           int vec_ok) {
+    Quad q;
+    if (!ly_quad(q, total, HW)) return;
+    const bool vec = vec_ok && q.cnt == 4;
+    const float kf = g ? g[0] * inv_cnt : 0.0f, kr = g ? g[1] * inv_cnt : 0.0f;
+    long long o1[4], o2[4], o2b[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o1[e] = q.pix[e]; o2[e] = q.pix[e] + q.n[e] * HW; o2b[e] = o2[e] + HW; }
+    float a0[4], a1[4], r[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sm[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    ld4(a, o2, vec, q.cnt, a0);
+    ld4(a, o2b, vec, q.cnt, a1);
+    if (g) {
+        ld4(rock, o1, vec, q.cnt, r);
+        ld4(sma, o1, vec, q.cnt, sm);
+    }
+    if (gc0) ld4(gc0, o1, vec, q.cnt, gc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float sf = ly_sigmoid(a1[e]), sb = ly_sigmoid(a0[e]);
+        const float s = sf + sb, nn = ly_clamp_eps(s);
+        float dc0 = gc[e];
+        if (g) {
+            const float m = 1.0f - sm[e], nr = 1.0f - r[e];
+            const float c0 = sf / nn;
+            dc0 += ly_smooth_l1_grad(c0 * nr * m - nr * m, kf) * m * nr;
+            dc0 += ly_smooth_l1_grad(c0 * r[e] * m - target * r[e] * m, kr) * m * r[e];
+        }
+        const float gnn = -dc0 * sf / (nn * nn);
+        const float gs = s >= LY_EPS ? gnn : 0.0f;
+        a1[e] = (dc0 / nn + gs) * (1.0f - sf) * sf;
+        a0[e] = gs * (1.0f - sb) * sb;
+    }
+    st4(da, o2, vec, q.cnt, a0);
+    st4(da, o2b, vec, q.cnt, a1);
+}
+
 static long long ly_blocks(long long total) { return (total + LY_PER_BLOCK - 1) / LY_PER_BLOCK; }
 static bool ly_sizes(int N, int H, int W, int min_hw) {
     return N > 0 && H >= min_hw && W >= min_hw && (long long)N * H * W < (1LL << 36);
@@ -460,6 +568,44 @@ SLR_EXPORT int slr_alpha_losses_backward(const float *a_start, const float *mask
                        mask_rock, small_motion_alpha, warped_alpha, norm, fluid_alpha_raw, losses, g_losses, d_a_start, d_fluid_alpha_raw,
                        total, HW, H, W, reweight, (float)(1.0 / (double)total), (float)(1.0 / ((double)N * H * (W - 1))),
                        (float)(1.0 / ((double)N * (H - 1) * W)), vec);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+SLR_EXPORT size_t slr_blend_alpha0_ws_bytes(int N, int H, int W) {
+    if (!ly_sizes(N, H, W, 1)) return 0;
+    return al256((size_t)ly_blocks((long long)N * H * W) * B0_SUMS * sizeof(double));
+}
+
+SLR_EXPORT int slr_blend_alpha0_forward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, float *c0,
+                                        float *values, float rock_target, int N, int H, int W, void *ws, size_t ws_bytes, void *stream) {
+    SLR_CHECK_ARG(a_start && mask_rock && small_motion_alpha && c0 && values, "null pointer");
+    SLR_CHECK_ARG(ly_sizes(N, H, W, 1), "sizes");
+    if (!ws || ws_bytes < slr_blend_alpha0_ws_bytes(N, H, W) || ((uintptr_t)ws & 7)) {
+        slr::set_error("%s: workspace: slr_blend_alpha0_ws_bytes(N, H, W) bytes, 8-byte aligned", __func__);
+        return SLR_E_WORKSPACE;
+    }
+    const long long HW = (long long)H * W, total = (long long)N * HW, blocks = ly_blocks(total);
+    const int vec = HW % 4 == 0 && !(((uintptr_t)a_start | (uintptr_t)mask_rock | (uintptr_t)small_motion_alpha | (uintptr_t)c0) & 15);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(blend_alpha0_forward_kernel, dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, a_start, mask_rock,
+                       small_motion_alpha, c0, (double *)ws, rock_target, total, HW, vec);
+    SLR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(blend_alpha0_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)ws, values, (int)blocks, (double)total);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+SLR_EXPORT int slr_blend_alpha0_backward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *g_c0,
+                                         const float *g_values, float *d_a_start, float rock_target, int N, int H, int W, void *stream) {
+    SLR_CHECK_ARG(a_start && mask_rock && small_motion_alpha && d_a_start, "null pointer");
+    SLR_CHECK_ARG(g_c0 || g_values, "null pointer: no gradient arrives");
+    SLR_CHECK_ARG(ly_sizes(N, H, W, 1), "sizes");
+    const long long HW = (long long)H * W, total = (long long)N * HW;
+    const int vec = HW % 4 == 0 && !(((uintptr_t)a_start | (uintptr_t)mask_rock | (uintptr_t)small_motion_alpha | (uintptr_t)g_c0 |
+                                      (uintptr_t)d_a_start) & 15);
+    hipLaunchKernelGGL(blend_alpha0_backward_kernel, dim3((unsigned)ly_blocks(total)), dim3(LY_THREADS), 0, (hipStream_t)stream, a_start,
+                       mask_rock, small_motion_alpha, g_c0, g_values, d_a_start, rock_target, (float)(1.0 / (double)total), total, HW, vec);
     SLR_CHECK_LAUNCH();
     return 0;
 }
