@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 25
+#define SLR_ABI_VERSION 26
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -1107,6 +1107,42 @@ int slr_blend_alpha0_forward(const float *a_start, const float *mask_rock, const
  * flows through the clamped sum (the convention of slr_layer_composite_backward). */
 int slr_blend_alpha0_backward(const float *a_start, const float *mask_rock, const float *small_motion_alpha, const float *g_c0,
                               const float *g_values, float *d_a_start, float rock_target, int N, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------ LPIPS of the clip evaluation (ABI 26; csrc/lpips.hip)
+ * The reference's tables are LPIPS: evaluation/animation/eval_CLAW.py:24,37 calls lpips.LPIPS(net='alex', version='0.1') on every frame
+ * pair.  Trunk and scaling constants: models/networks/pretrained_networks.py:45-46 and :154-196 (torchvision's alexnet.features cut
+ * after each ReLU); the linear heads are those of the lpips package.  Everything here is fp32 (the convolutions on
+ * v_mfma_f32_32x32x2_f32: fp32 operands, products and accumulation), deterministic (fixed order, no atomics), and a result depends on
+ * its own image only.  The three 3x3 convolutions of the trunk run on slr_conv3x3_forward with SLR_CONV_F32. */
+
+/* The input of the trunk (lpips' ScalingLayer = pretrained_networks.py:45-46, 73-74): out [N,3,H,W] NCHW = (x - shift) / scale, with
+ * normalize = 1 ((2 x - 1) - shift) / scale (lpips' normalize=True: images in [0,1]).  img: float [N,3,H,W] (u8 = 0) or uint8 [N,H,W,3]
+ * (u8 = 1; x = v / 255.0f first, in either mode). */
+int slr_lpips_prep(const void *img, int u8, int normalize, float *out, int N, int H, int W, void *stream);
+
+/* nn.Conv2d(Cin, Cout, K, stride, padding) + bias for (K, stride, padding) = (11, 4, 2) and (5, 1, 2): features.0 and features.3 of
+ * torchvision's alexnet (pretrained_networks.py:161-166).  Weights w [Cout,Cin,K,K] are prepared once into fragment order
+ * (slr_convkxk_f32_weights into slr_convkxk_weight_bytes(Cout, Cin, K) bytes; 0 for sizes it refuses).  in [N,Cin,H,W] NCHW
+ * (in_b8 = 0) or channel-blocked [N,Cin/8,H,W,8] (in_b8 = 1, Cin % 8 == 0); out [N,Cout,OH,OW], O. = (. + 2 padding - K) / stride + 1,
+ * channel-blocked [N,Cout/8,OH,OW,8], Cout % 8 == 0, RAW: the ReLU belongs to the consumer.  Any H, W >= 1 with OH, OW >= 1;
+ * N H W < 2^31; channel-blocked tensors are 16-byte aligned. */
+size_t slr_convkxk_weight_bytes(int Cout, int Cin, int K);
+int slr_convkxk_f32_weights(const float *w, void *wfrag, int Cout, int Cin, int K, void *stream);
+int slr_convkxk_forward(const float *in, const void *wfrag, const float *bias, float *out, int N, int Cin, int Cout, int H, int W, int K,
+                        int stride, int pad, int in_b8, void *stream);
+
+/* nn.ReLU + nn.MaxPool2d(3, stride 2) of torchvision's alexnet.features (floor mode, no padding: 179 x 319 -> 89 x 159):
+ * in [N,C,H,W] -> out [N,C,(H-3)/2+1,(W-3)/2+1], both channel-blocked, C % 8 == 0, H, W >= 3, 16-byte aligned.  A window that holds a
+ * NaN gives NaN, as slr_relu_maxpool2x2_b8 does. */
+int slr_relu_maxpool3x3s2_b8(const float *in, float *out, int N, int C, int H, int W, void *stream);
+
+/* One layer of LPIPS: with f = relu(raw features) and n(f) = f / (sqrt(sum_c f_c^2) + 1e-10),
+ *   out[n] = mean_hw sum_c w[c] (n(f0)_c - n(f1)_c)^2        (lpips: normalize_tensor, NetLinLayer without bias, spatial_average)
+ * f0, f1 [N,C,H,W] raw, channel-blocked (C % 8 == 0); w [C] (any sign), 16-byte aligned; out [N].  Two all-zero feature vectors at a
+ * pixel contribute exactly 0; equal features give exactly 0.  ws: slr_lpips_distance_ws_bytes(N, H, W) bytes, 8-byte aligned. */
+size_t slr_lpips_distance_ws_bytes(int N, int H, int W);
+int slr_lpips_distance(const float *f0, const float *f1, const float *w, float *out, int N, int C, int H, int W, void *ws,
+                       size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 25
+ABI_VERSION = 26
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -150,6 +150,13 @@ SIGNATURES = {
     "slr_blend_alpha0_ws_bytes": (_sz, [_i, _i, _i]),
     "slr_blend_alpha0_forward": (_i, [_fp] * 5 + [_f, _i, _i, _i, _vp, _sz, _vp]),
     "slr_blend_alpha0_backward": (_i, [_fp] * 6 + [_f, _i, _i, _i, _vp]),
+    "slr_lpips_prep": (_i, [_vp, _i, _i, _fp, _i, _i, _i, _vp]),
+    "slr_convkxk_weight_bytes": (_sz, [_i, _i, _i]),
+    "slr_convkxk_f32_weights": (_i, [_fp, _vp, _i, _i, _i, _vp]),
+    "slr_convkxk_forward": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "slr_relu_maxpool3x3s2_b8": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
+    "slr_lpips_distance_ws_bytes": (_sz, [_i, _i, _i]),
+    "slr_lpips_distance": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(SIGNATURES)
 

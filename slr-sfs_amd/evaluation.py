@@ -12,7 +12,14 @@ import torch.nn.functional as F
 
 from . import io
 
-KEYS = ("Perceptual", "PSNR", "SSIM")         # metric.json without LPIPS: it needs the lpips package's weights and AlexNet (not built)
+KEYS = ("Perceptual", "PSNR", "SSIM")         # metric.json without LPIPS (no LPIPS weights given)
+KEYS_LPIPS = ("LPIPS",) + KEYS                # ... and with it (metrics.LPIPSAlex): the reference's own key order, eval_CLAW.py:83-87
+
+
+def metric_keys(perceptual, lpips):
+    """The keys of metric.json for the metrics that were computed, in the reference's order: PSNR and SSIM always, Perceptual / LPIPS
+    with their networks."""
+    return tuple(k for k in KEYS_LPIPS if not ((k == "LPIPS" and not lpips) or (k == "Perceptual" and not perceptual)))
 
 
 def read_frames(frame_dir, n):
@@ -114,8 +121,9 @@ def fluid_composite(pred_u8, image, mask):
 
 
 def aggregate(per_scene, keys=KEYS):
-    """metric.json of eval_CLAW.py:79-160 (without LPIPS): {name: {key: [per-frame values]}} -> Total<key> (np.mean over every frame
-    of every scene), Total<key>_std (np.std), <key> {name: mean} and <key>_std {name: std}, in the reference's key order."""
+    """metric.json of eval_CLAW.py:79-160 (keys=KEYS_LPIPS: all of it; the default: without LPIPS): {name: {key: [per-frame values]}} ->
+    Total<key> (np.mean over every frame of every scene), Total<key>_std (np.std), <key> {name: mean} and <key>_std {name: std}, in the
+    reference's key order."""
     res = {}
     for k in keys:
         res[f"Total{k}"] = {}

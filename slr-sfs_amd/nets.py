@@ -856,6 +856,45 @@ class Conv4x4s2(nn.Module):
         return bn(y) if bn is not None else y
 
 
+class ConvKxK(nn.Module):
+    """nn.Conv2d(cin, cout, k, stride, padding) + bias for the two shapes of AlexNet that no other kernel here covers, (k, stride,
+    padding) = (11, 4, 2) and (5, 1, 2) (slr_convkxk_forward: fp32 MFMA, the arithmetic of the fp32 rung).  The output is RAW and
+    channel-blocked, like a ``Conv`` with OUT_B8; ``in_b8``: so is the input.  Device tensors only."""
+
+    def __init__(self, cin, cout, k, stride, padding):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, k, k), requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros(cout), requires_grad=False)
+        self.cin, self.k, self.stride, self.pad = cin, k, stride, padding
+        nn.init.normal_(self.weight, std=math.sqrt(1.0 / (cin * k * k)))
+
+    def _frag(self):
+        w = self.weight
+
+        def make():
+            buf = torch.empty(_lib.lib().slr_convkxk_weight_bytes(w.shape[0], w.shape[1], self.k), dtype=torch.uint8, device=w.device)
+            _lib.call("slr_convkxk_f32_weights", w.device, w, buf, w.shape[0], w.shape[1], self.k)
+            return buf
+        return _cached(self, "_wfrag", make, w)
+
+    def out_size(self, H, W):
+        return (H + 2 * self.pad - self.k) // self.stride + 1, (W + 2 * self.pad - self.k) // self.stride + 1
+
+    def forward(self, x, in_b8=False):
+        if not x.is_cuda:
+            raise NotImplementedError("slr_sfs_amd.nets.ConvKxK runs on ROCm device tensors only (no CPU path)")
+        _lib.require_device(x)
+        N, cin, H, W = x.shape
+        cout = self.weight.shape[0]
+        OH, OW = self.out_size(H, W)
+        if cin != self.cin or OH < 1 or OW < 1:
+            raise ValueError(f"ConvKxK({self.cin}, {cout}, {self.k}, {self.stride}, {self.pad}): input {tuple(x.shape)} gives no output")
+        out = torch.empty(N, cout, OH, OW, device=x.device, dtype=x.dtype)
+        _lib.call("slr_convkxk_forward", x.device, x, self._frag(), self.bias, out, N, cin, cout, H, W, self.k, self.stride, self.pad,
+                  int(bool(in_b8)))
+        return out
+
+
 class BNConv3x3(Conv):
     """3x3 convolution followed by an eval BatchNorm (or nothing): on a device the BN is folded into the weights and bias of ONE fp32-rung
     3x3 kernel (prepared once per weight / statistics version); the torch composition runs the two stages as the reference does."""

@@ -56,7 +56,11 @@ def main():
                          "the device (PSNR, SSIM; tools/evaluate.py's metric.json for this one scene), from the uint8 frames written")
     ap.add_argument("--metrics-json", default=None, help="where --gt-frames writes its JSON (default OUTDIR/../metric.json)")
     ap.add_argument("--perceptual-weights", default=None, help="with --gt-frames: a torchvision VGG16 state dict, adds Perceptual")
+    ap.add_argument("--lpips-alexnet", default=None, help="with --gt-frames and --lpips-linear: a torchvision AlexNet state dict, adds LPIPS")
+    ap.add_argument("--lpips-linear", default=None, help="the lpips package's weights/v0.1/alex.pth (lin0 .. lin4)")
     a = ap.parse_args()
+    if bool(a.lpips_alexnet) != bool(a.lpips_linear):
+        ap.error("--lpips-alexnet and --lpips-linear go together: the trunk and the linear heads of LPIPS are two files")
     rank, world, dev = init_ranks()
     model = runner.load_model(a.ckpt, a.v1, dev, motion_ckpt=a.motion_ckpt)
     points = None if a.hint_points is None else [tuple(int(v) for v in p.split(",")) for p in a.hint_points.split(";")]
@@ -71,8 +75,9 @@ def main():
                 raise ValueError(f"--gt-frames {a.gt_frames}: fewer than {frames.shape[0]} frames")
             gt = torch.from_numpy(evaluation.resize_like_reference(gt, tuple(frames.shape[1:3]))).to(frames.device)
             vgg = metrics.PerceptualVGG16.from_file(a.perceptual_weights, frames.device) if a.perceptual_weights else None
-            per = {k: v.cpu().tolist() for k, v in metrics.evaluate_clip(frames.contiguous(), gt, perceptual=vgg).items()}
-            res = evaluation.aggregate({a.name: per}, evaluation.KEYS if vgg is not None else ("PSNR", "SSIM"))
+            lp = metrics.LPIPSAlex.from_files(a.lpips_alexnet, a.lpips_linear, frames.device) if a.lpips_alexnet else None
+            per = {k: v.cpu().tolist() for k, v in metrics.evaluate_clip(frames.contiguous(), gt, perceptual=vgg, lpips=lp).items()}
+            res = evaluation.aggregate({a.name: per}, evaluation.metric_keys(vgg is not None, lp is not None))
             path = a.metrics_json or os.path.join(a.outdir, "..", "metric.json")
             with open(path, "w") as f:
                 json.dump(res, f)
