@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 26
+#define SLR_ABI_VERSION 27
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -504,6 +504,34 @@ int slr_pconv3x3_forward_skipout(const float *x, const float *pre_scale, const f
                                  const float *next_scale, const float *next_shift, float *out, float *um_out,
                                  int N, int Cin, int Cout, int H, int W,
                                  const float *skip_w4, float *skip_out, int layout, void *stream);
+
+/* ABI 27.  The narrow end without its widest tensor.  A 128-channel block's second partial convolution whose result has ONE pair of
+ * readers -- the next block's 128 -> 3 first convolution and its 1x1 skip -- never writes that result: a 3x3 convolution onto 3 channels
+ * is a per-pixel linear map onto 27 columns (tap * 3 + co) followed by a gather of nine shifted columns, the map needs no halo, and its
+ * operand is what the wide kernel holds in its accumulators when it finishes.
+ *   slr_pconv3x3_forward_tail: slr_pconv3x3_forward (no prologue; x, residual channel-blocked; split-f16 rung; Cout = 128) up to and
+ *     including the residual add, o; then per pixel  Z[tap * 3 + co] = sum_ci relu(o * tail_scale - tail_shift)[ci] * um * w_aa[co, ci, tap]
+ *     (the next block's first BN, the update mask just computed) and  Z[27 + co] = sum_ci o[ci] * w_b[co, ci],  both operands scaled by
+ *     xscale, clamped, counted (slr_conv_saturation_count) and split like every staged activation, products in the kernels' order.
+ *     z_out [N,32,H,W] fp32 planar, in the operands' scale (x xscale x the branch's wscale), planes 30-31 zero; um_out as always.
+ *   slr_conv_tail_weights: w_aa [3,Cin,3,3] and w_b [3,Cin,1,1] -> the split column weights, slr_conv_tail_weight_bytes(Cin) bytes
+ *     (Cin: the wide convolution's OUTPUT channels, a multiple of 32), [tile of 32 channels][activated | raw][chunk of 16][hi | lo][lane 64][8];
+ *     each branch has its own power-of-two wscale.  slr_conv_tail_weight_source: (operand, half, row of the tile, input channel) of one
+ *     element of that buffer -- the layout, on the host.
+ *   slr_narrow_gather: raw[co] = sum over the nine taps, ascending, of plane tap * 3 + co shifted by the tap (zero outside the image),
+ *     then the partial epilogue of the <= 4-channel kernel operation for operation with `mask` [N,1,H,W] (the wide kernel's um_out) and
+ *     Cin input channels behind every mask value: out [N,3,H,W] = relu(((raw * ratio + bias) * um) * next_scale - next_shift) * um
+ *     (next_scale = NULL: without), um_out [N,1,H,W], skip_out [N,3,H,W] = Z[27 + co] (+ skip_bias): what slr_pconv3x3_forward_skipout
+ *     returns, to the rounding of a different order of the same sums. */
+size_t slr_conv_tail_weight_bytes(int Cin);
+int slr_conv_tail_weight_source(int Cin, int element, int *operand, int *half, int *row, int *ci);
+int slr_conv_tail_weights(const float *w_aa, const float *w_b, void *wtail, int Cin, float wscale_aa, float wscale_b, void *stream);
+int slr_pconv3x3_forward_tail(const float *x, const float *mask, const void *wsplit, float wscale, float xscale, const float *bias,
+                              const float *residual /* [N,Cout,H,W] channel-blocked, or NULL */, const float *tail_scale, const float *tail_shift,
+                              const void *wtail, float *z_out, float *um_out, int N, int Cin, int Cout, int H, int W, void *stream);
+int slr_narrow_gather(const float *z, const float *mask, const float *bias, const float *next_scale, const float *next_shift,
+                      const float *skip_bias /* [3] or NULL */, float *out, float *um_out, float *skip_out, int N, int Cin, int H, int W,
+                      float wscale, float skip_wscale, float xscale, void *stream);
 
 /* 1x1 convolution (skip branch of the residual blocks, models/layers/blocks.py:192-193,243-247) on the same
  * split-f16 arithmetic: out = conv1x1(in) + bias.  HBM-bound, no LDS.  Weights prepared once per layer with

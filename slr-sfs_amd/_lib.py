@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 26
+ABI_VERSION = 27
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -68,6 +68,11 @@ SIGNATURES = {
     "slr_pconv3x3_forward_skip": (_i, [_fp, _fp, _fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp, _i, _f, _vp, _sz, _i, _vp]),
     "slr_conv3x3_forward_skipout": (_i, [_fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _f, _fp, _fp, _fp, _fp, _fp, _i, _vp]),
     "slr_pconv3x3_forward_skipout": (_i, [_fp, _fp, _fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _i, _vp]),
+    "slr_conv_tail_weight_bytes": (_sz, [_i]),
+    "slr_conv_tail_weight_source": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "slr_conv_tail_weights": (_i, [_fp, _fp, _vp, _i, _f, _f, _vp]),
+    "slr_pconv3x3_forward_tail": (_i, [_fp, _fp, _vp, _f, _f, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "slr_narrow_gather": (_i, [_fp] * 9 + [_i, _i, _i, _i, _f, _f, _f, _vp]),
     "slr_conv1x1_weight_bytes": (_sz, [_i, _i]),
     "slr_conv1x1_split_weights": (_i, [_fp, _vp, _i, _i, _f, _vp]),
     "slr_conv1x1_f32_weights": (_i, [_fp, _vp, _i, _i, _vp]),

@@ -95,6 +95,8 @@ struct ConvArgs {
     float *pool_row, *pool_col;
     int tiles_y, resample;   // resample: 0 none, 1 POOL, 2 UPS
     float *skip_out;       // conv3x3_few_kernel<.., SKP>: [N,Cout,H,W] = conv1x1(in) + skip_bias with skip_w = plain fp32 [Cin][4] weights
+    // TAIL instantiation (slr_pconv3x3_forward_tail; no new fields, so no other kernel's arguments move): out = Z [N,32,H,W], residual
+    // channel-blocked and added BEFORE next_scale / next_shift (here the NEXT block's first BN), skip_w = the tail's column weights
 };
 
 // padded channel counts of the weight buffer (shared by the split and the forward entry points)
@@ -124,9 +126,12 @@ constexpr int CV_KSTR = 260;                       // F32, skip fills: floats pe
 // the write of its result and the read of it as the residual are gone.
 // POOL (with SKIP, 128-channel workgroup rows): the "Down" block's average pool in the epilogue -- see the end of the kernel.
 // UPS (likewise): the "Up" block's x2 bilinear up-sampling in the epilogue.
-template <int CPW, int WCO, bool PRE, bool INB8, bool F32 = false, bool SKIP = false, bool POOL = false, bool UPS = false>
+// TAIL (128-channel rows, channel-blocked input, no prologue, partial epilogue with a channel-blocked residual): the result's only readers are
+// the NEXT block's 128 -> 3 convolution and 1x1 skip, and it is never written -- see the tail phase behind the main loop.
+template <int CPW, int WCO, bool PRE, bool INB8, bool F32 = false, bool SKIP = false, bool POOL = false, bool UPS = false, bool TAIL = false>
 __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a) {
     constexpr int WPX = 4 / WCO, PT = CV_H / WPX;
+    static_assert(!TAIL || (CPW == 1 && WCO == 4 && !PRE && INB8 && !F32 && !SKIP && !POOL && !UPS), "the tail phase: one instantiation");
     static_assert(!(POOL || UPS) || (SKIP && WCO == 4 && !(POOL && UPS)), "the resampling epilogues: a wave holds all 8 rows of its channel tile");
     static_assert(!F32 || CPW == 1, "the fp32 rung runs one 32-channel tile per wave");
     static_assert(!SKIP || (CPW == 1 && INB8), "the skip phase: one tile per wave, channel-blocked main input");
@@ -618,6 +623,134 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv3x3_split_kernel(ConvArgs a
             }
             __syncthreads();
         }
+    }
+
+    if constexpr (TAIL) {
+        // ---- tail phase.  A 3x3 convolution onto 3 channels is a per-pixel linear map onto 27 columns (tap, co) followed by a gather of
+        // the nine shifted columns, and the map needs no halo:  Y[px, tap * 3 + co] = sum_ci act(o)[px, ci] * W[co, ci, tap]  with
+        // act(o) = relu(o * scale - shift) * um (the next block's first BN and the update mask computed right here); the next block's 1x1
+        // skip on the raw o adds columns 27-29.  The per-pixel operand is what this kernel holds in its accumulators: in the D layout a lane
+        // has, for its pixel, channels 8q + 4 * (lane >> 5) + 0..3 (q = 0..3) of the wave's 32, so registers 8c .. 8c + 7 of a row ARE the B
+        // fragment of chunk c, given column weights whose K slots are permuted to match (conv_tail_source).  Per row: this kernel's epilogue
+        // (partial convolution, residual), the two operands scaled, clamped, counted and split as stage_value does, 2 operands x 2 chunks x
+        // 3 products (w_lo x_hi, w_hi x_lo, w_hi x_hi) into ONE 32 x 32 tile (the operands' weight rows are disjoint, so each row keeps its
+        // own branch's scale).  The four waves' partial sums over their 32 channels meet in LDS (the staging buffers are free), two rows at
+        // a time, and leave as Z [N,32,H,W] in the operands' scale for narrow_gather_kernel.  `out` is Z; the result itself is not written.
+        constexpr int ZS = 36;                             // floats per row of a wave's tile in LDS (16-byte aligned rows)
+        static_assert(2 * 4 * 32 * ZS * 4 <= XRAW, "two rows of four partial tiles live in the staging buffers");
+        float *zred = reinterpret_cast<float *>(xraw);    // [row of the pair][wave][column (tap, co)][pixel]
+        const h8 *tw = a.skip_w + (size_t)cot0 * 512 + lane;         // [tile][operand][chunk][half][64 lanes]
+        h8 ta[2][2][2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) ta[p][c][h] = tw[((p * 2 + c) * 2 + h) * 64];
+        // bias and the next block's BN tables by output channel: in LDS (the prologue table is free without a prologue), read row by row --
+        // 48 more registers next to 128 accumulators, the column weights and a row's operands do not fit
+        float4 *ebt = &pss4[0][0];                         // [bias | scale | shift][Cout / 4]
+        if (tid < 128) {
+            float *t = reinterpret_cast<float *>(ebt);
+            t[tid] = a.bias[tid]; t[128 + tid] = a.next_scale[tid]; t[256 + tid] = a.next_shift[tid];
+        }
+        __syncthreads();
+        const float unscale = a.unscale, mscale = a.mask_scale, winsize = a.winsize, xsc = a.xscale;
+        const int ox = x0 + bcol;
+        const bool has_res = a.residual != nullptr;
+        const bool zvec = (a.W % 4 == 0) && !((uintptr_t)a.out & 15);
+#pragma unroll
+        for (int pp = 0; pp < PT / 2; ++pp) {
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+                const int pt = pp * 2 + h2;
+                const int oy = y0 + pt;
+                const bool ok = (ox < a.W) & (oy < a.H);
+                const size_t pix = ok ? (size_t)oy * a.W + ox : 0;
+                float box = 0.0f;                              // conv(mask, ones): 3x3 box sum, zero padded (partialconv2d.py:61)
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) box += mpl[(pt + dy) * CV_HW + bcol + dx];
+                const float u = box * mscale;
+                const float um = fminf(fmaxf(u, 0.0f), 1.0f);
+                const float ratio = (1.0f / (u + 1e-8f)) * winsize * um;
+                if (ok && a.um_out && wc == 0 && bgrp == 0) a.um_out[(size_t)n * HW + pix] = um;
+                float o[16], esc[16], esh[16];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c4 = cot0 * 8 + 2 * q + bgrp;    // channels 8q + 4 * (lane >> 5) + 0..3 of the wave's tile
+                    const float4 b4 = ebt[c4], s4 = ebt[32 + c4], h4 = ebt[64 + c4];
+                    const float eb[4] = {b4.x, b4.y, b4.z, b4.w};
+                    esc[4 * q] = s4.x; esc[4 * q + 1] = s4.y; esc[4 * q + 2] = s4.z; esc[4 * q + 3] = s4.w;
+                    esh[4 * q] = h4.x; esh[4 * q + 1] = h4.y; esh[4 * q + 2] = h4.z; esh[4 * q + 3] = h4.w;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[4 * q + e] = ((acc[0][pt][4 * q + e] * unscale) * ratio + eb[e]) * um;       // :72-74
+                }
+                if (has_res) {                                                                                        // blocks.py:248
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 rv = *reinterpret_cast<const float4 *>(&a.residual[(((size_t)n * (a.Cout >> 3) + cot0 * 4 + q) * HW + pix) * 8 + 4 * bgrp]);
+                        o[4 * q] += rv.x; o[4 * q + 1] += rv.y; o[4 * q + 2] += rv.z; o[4 * q + 3] += rv.w;
+                    }
+                }
+                const float live = ok ? xsc : 0.0f;            // validity x the pre-scale of the split (pixels outside the image: zero, never counted)
+                h8 bh[2][2], bl[2][2];                         // [operand: activated | raw][chunk]
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float two[2] = {fmaxf(o[r] * esc[r] - esh[r], 0.0f) * um, o[r]};     // blocks.py:233-236 of the next block | its skip's input
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        const float v = __builtin_amdgcn_fmed3f(two[p] * live, -65472.0f, 65472.0f);                    // (the range guard of stage_value)
+                        sat |= __ballot(fabsf(v) >= 65472.0f);
+                        const _Float16 h = (_Float16)v;
+                        bh[p][r >> 3][r & 7] = h;
+                        bl[p][r >> 3][r & 7] = (_Float16)(v - (float)h);
+                    }
+                }
+                f16v z;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) z[r] = 0.0f;
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta[p][c][1], bh[p][c], z, 0, 0, 0);
+                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta[p][c][0], bl[p][c], z, 0, 0, 0);
+                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta[p][c][0], bh[p][c], z, 0, 0, 0);
+                    }
+                float *zw = zred + ((h2 * 4 + wave) * 32 + 4 * bgrp) * ZS + bcol;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) zw[((r & 3) + 8 * (r >> 2)) * ZS] = z[r];
+            }
+            __syncthreads();
+            // the pair's two rows of Z: 32 columns x 32 pixels each, 4 pixels per work-item; waves added in ascending order
+            const int m = tid >> 3, x4 = (tid & 7) * 4;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+                const int oy = y0 + pp * 2 + h2;
+                const float *zr = zred + (h2 * 4 * 32 + m) * ZS + x4;
+                float4 s = *reinterpret_cast<const float4 *>(zr);
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const float4 t = *reinterpret_cast<const float4 *>(zr + w * 32 * ZS);
+                    s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+                }
+                if (oy < a.H) {
+                    float *zo = a.out + (((size_t)n * 32 + m) * a.H + oy) * a.W + x0 + x4;
+                    if (zvec && x0 + x4 + 3 < a.W) *reinterpret_cast<float4 *>(zo) = s;
+                    else {
+                        const float sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (x0 + x4 + e < a.W) zo[e] = sv[e];
+                    }
+                }
+            }
+            if (pp + 1 < PT / 2) __syncthreads();
+        }
+        if (a.sat && sat != 0ull && lane == 0) atomicAdd(a.sat, 1u);
+        return;
     }
 
     if (!F32 && a.sat && sat != 0ull && lane == 0) atomicAdd(a.sat, 1u);   // an activation left the f16 range (stage_value)
@@ -1134,6 +1267,79 @@ __global__ __launch_bounds__(256) void upsample_fix_kernel(float *__restrict__ o
     o[1] = make_float4(r[4], r[5], r[6], r[7]);
 }
 
+// ---- the narrow end behind a TAIL kernel -----------------------------------------------------------------------------------------------
+constexpr int CT_CO = 3;                               // output channels of the narrow convolution the tail serves
+constexpr int CT_ROWS = 32;                            // planes of Z: 27 columns (tap * 3 + co), 3 of the skip, 2 zero
+constexpr int CT_SKIP0 = 9 * CT_CO;                    // first skip row
+
+// Element e of the tail's column weights, [tile of 32 input channels][operand: activated | raw][chunk][hi | lo][lane 64][8]: the row m of
+// the 32 x 32 tile and the input channel ci it multiplies.  The K slots follow the D layout of the kernel that forms the operand:
+// lane (m, g = lane >> 5), slot j of chunk c is the channel in accumulator register 8c + j of a lane of half g, 16c + 8 (j >> 2) + 4g + (j & 3).
+__host__ __device__ inline void conv_tail_source(int e, int &operand, int &half, int &m, int &ci) {
+    const int j = e & 7, l = (e >> 3) & 63;
+    half = (e >> 9) & 1;
+    const int c = (e >> 10) & 1;
+    operand = (e >> 11) & 1;
+    const int tile = e >> 12, g = l >> 5;
+    m = l & 31;
+    ci = tile * 32 + c * 16 + 8 * (j >> 2) + 4 * g + (j & 3);
+}
+
+// w_aa [3,Cin,3,3] (rows tap * 3 + co of the activated operand) and w_b [3,Cin,1,1] (rows 27 + co of the raw operand), each scaled by its
+// own power of two, split; every other row zero
+__global__ __launch_bounds__(256) void conv_tail_weights_kernel(const float *__restrict__ waa, const float *__restrict__ wb, _Float16 *__restrict__ ws,
+                                                                int Cin, float wscale_aa, float wscale_b) {
+    const int total = (Cin >> 5) * 4096;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
+        int operand, half, m, ci;
+        conv_tail_source(e, operand, half, m, ci);
+        float x = 0.0f;
+        if (operand == 0 && m < CT_SKIP0) x = waa[((size_t)(m % CT_CO) * Cin + ci) * 9 + m / CT_CO] * wscale_aa;
+        if (operand == 1 && m >= CT_SKIP0 && m < CT_SKIP0 + CT_CO) x = wb[(size_t)(m - CT_SKIP0) * Cin + ci] * wscale_b;
+        const _Float16 h = (_Float16)x;
+        ws[e] = half ? (_Float16)(x - (float)h) : h;
+    }
+}
+
+// The gather: raw[co] = the nine shifted planes tap * 3 + co of Z in ascending tap order (neighbours outside the image count as zero), then
+// conv3x3_few_kernel's partial epilogue operation for operation (conv_few.hpp) -- box sum of the mask, um, ratio, (raw * ratio + bias) * um,
+// relu(. * next_scale - next_shift) * um -- and the skip = planes 27-29 (+ skip_bias).  One work-item per pixel; HBM-bound (32 planes read once,
+// the shifted re-reads are cache hits).
+__global__ __launch_bounds__(256) void narrow_gather_kernel(const float *__restrict__ z, const float *__restrict__ mask, const float *__restrict__ bias,
+                                                            const float *__restrict__ next_scale, const float *__restrict__ next_shift,
+                                                            const float *__restrict__ skip_bias, float *__restrict__ out, float *__restrict__ um_out,
+                                                            float *__restrict__ skip_out, int H, int W, float mask_scale, float winsize,
+                                                            float unscale, float skip_unscale) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    if (x >= W || y >= H) return;
+    const size_t HW = (size_t)H * W;
+    const float *zn = z + (size_t)n * CT_ROWS * HW, *mn = mask + (size_t)n * HW;
+    float raw[CT_CO] = {0.0f, 0.0f, 0.0f};
+    float box = 0.0f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+        const bool in = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W);
+        const size_t at = in ? (size_t)yy * W + xx : 0;
+        box += in ? mn[at] : 0.0f;
+#pragma unroll
+        for (int co = 0; co < CT_CO; ++co) raw[co] += in ? zn[(size_t)(tap * CT_CO + co) * HW + at] : 0.0f;
+    }
+    const size_t pix = (size_t)y * W + x;
+    const float u = box * mask_scale;                      // exact small integers in fp32
+    const float um = clamp01_nan(u);
+    const float ratio = (1.0f / (u + 1e-8f)) * winsize * um;
+    um_out[(size_t)n * HW + pix] = um;
+#pragma unroll
+    for (int co = 0; co < CT_CO; ++co) {
+        float o = ((raw[co] * unscale) * ratio + bias[co]) * um;                               // partialconv2d.py:72-74
+        if (next_scale) o = fmaxf(o * next_scale[co] - next_shift[co], 0.0f) * um;            // blocks.py:233-236
+        out[((size_t)n * CT_CO + co) * HW + pix] = o;
+        const float s = zn[(size_t)(CT_SKIP0 + co) * HW + pix] * skip_unscale;
+        skip_out[((size_t)n * CT_CO + co) * HW + pix] = skip_bias ? s + skip_bias[co] : s;
+    }
+}
+
 // w [Cout,Cin,k,k] fp32 (taps = k*k = 9 or 1) -> split f16 weights in fragment order over the PADDED
 // channel counts (zero weights for the padding), scaled by wscale (a power of two)
 __global__ __launch_bounds__(256) void conv_split_weights_kernel(const float *__restrict__ w, _Float16 *__restrict__ ws,
@@ -1568,7 +1774,7 @@ static constexpr bool conv_split_built() {
            !(F32 && SKIP && WCO != 4);
 }
 
-static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipStream_t st) {
+static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipStream_t st, bool tail = false) {
     const bool in_b8 = (layout & SLR_CONV_IN_B8) != 0, f32 = (layout & SLR_CONV_F32) != 0, wino = (layout & SLR_CONV_WINO) != 0;
     const bool pre = a.pre != PRE_NONE;
     if (int e = check_xscale(xscale)) return e;
@@ -1615,6 +1821,12 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
     // half of <2,2> (+3..5 % measured); 64: 1 tile x 4 rows per wave, half the weight-fragment loads of <2,1> (+4 %).  NCHW input with a
     // prologue: 64-channel rows at most (see conv_split_built; no network on the path uses it: wide layers read channel-blocked
     // activations).  The weight buffer is indexed by 32-channel tiles, so any row width reads it.
+    if (tail) {                                         // (slr_pconv3x3_forward_tail has checked what the one instantiation needs)
+        hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, true, false, false, false, false, true>),
+                           dim3(a.tiles_x * ((a.H + CV_H - 1) / CV_H), 1, a.N), dim3(CV_THREADS), 0, st, a);
+        SLR_CHECK_LAUNCH();
+        return 0;
+    }
     int ct = conv_cout_tile(a.Cout);
     if (ct == 128 && pre && !in_b8) ct = 64;
     const dim3 grid(a.tiles_x * ((a.H + CV_H - 1) / CV_H), conv_cout_pad(a.Cout) / ct, a.N);
@@ -1729,4 +1941,66 @@ SLR_EXPORT int slr_pconv3x3_forward_skipout(const float *x, const float *pre_sca
     const SkipOp sk = {nullptr, skip_w4, nullptr, 0, 1.0f, nullptr, 0, skip_out};
     return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
                        N, Cin, Cout, H, W, &sk, layout, stream);
+}
+
+// ---- the narrow end: block i's second partial convolution with the tail phase, and the gather (ABI 27) ---------------------------------
+
+SLR_EXPORT size_t slr_conv_tail_weight_bytes(int Cin) {
+    if (Cin <= 0 || Cin % 32 || Cin > CV_MAXCIN) return 0;
+    return (size_t)(Cin >> 5) * 4096 * sizeof(_Float16);
+}
+
+SLR_EXPORT int slr_conv_tail_weight_source(int Cin, int element, int *operand, int *half, int *row, int *ci) {
+    SLR_CHECK_ARG(operand && half && row && ci, "null pointer");
+    SLR_CHECK_ARG(Cin > 0 && Cin % 32 == 0 && element >= 0 && element < (Cin >> 5) * 4096, "element of a buffer of slr_conv_tail_weight_bytes(Cin)");
+    conv_tail_source(element, *operand, *half, *row, *ci);
+    return 0;
+}
+
+SLR_EXPORT int slr_conv_tail_weights(const float *w_aa, const float *w_b, void *wtail, int Cin, float wscale_aa, float wscale_b, void *stream) {
+    SLR_CHECK_ARG(w_aa && w_b && wtail, "null pointer");
+    SLR_CHECK_ARG(Cin > 0 && Cin % 32 == 0 && Cin <= CV_MAXCIN, "Cin: a multiple of 32, at most 1024");
+    SLR_CHECK_ARG(wscale_aa > 0.0f && wscale_b > 0.0f, "wscale");
+    SLR_CHECK_ARG(!((uintptr_t)wtail & 15), "16-byte aligned buffer");
+    hipLaunchKernelGGL(conv_tail_weights_kernel, dim3(((Cin >> 5) * 4096 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_aa, w_b,
+                       (_Float16 *)wtail, Cin, wscale_aa, wscale_b);
+    SLR_CHECK_LAUNCH();
+    return 0;
+}
+
+SLR_EXPORT int slr_pconv3x3_forward_tail(const float *x, const float *mask, const void *wsplit, float wscale, float xscale, const float *bias,
+                                         const float *residual, const float *tail_scale, const float *tail_shift, const void *wtail,
+                                         float *z_out, float *um_out, int N, int Cin, int Cout, int H, int W, void *stream) {
+    SLR_CHECK_ARG(x && mask && wsplit && bias && tail_scale && tail_shift && wtail && z_out, "null pointer");
+    SLR_CHECK_ARG(Cout == 128, "the tail phase is built for 128 output channels");
+    if (int e = conv_check_dims(N, Cin, Cout, H, W)) return e;
+    SLR_CHECK_ARG(Cin % 8 == 0 && !(((uintptr_t)x | (uintptr_t)residual | (uintptr_t)wtail) & 15),
+                  "channel-blocked input and residual: Cin % 8 == 0, 16-byte aligned tensors and tail weights");
+    SLR_CHECK_ARG(!((uintptr_t)z_out & 3), "4-byte aligned Z");
+    ConvArgs a = {};
+    a.in = x; a.w = (const h8 *)wsplit; a.bias = bias; a.out = z_out;
+    a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
+    a.pre = PRE_NONE; a.mask = mask;
+    a.partial = 1;
+    a.mask_scale = (float)Cin;
+    a.winsize = (float)Cin * 9.0f;
+    a.residual = residual; a.next_scale = tail_scale; a.next_shift = tail_shift; a.um_out = um_out;
+    a.out_b8 = 1; a.res_b8 = 1;
+    a.skip_w = (const h8 *)wtail;
+    return conv_launch(a, wscale, xscale, SLR_CONV_IN_B8, (hipStream_t)stream, true);
+}
+
+SLR_EXPORT int slr_narrow_gather(const float *z, const float *mask, const float *bias, const float *next_scale, const float *next_shift,
+                                 const float *skip_bias, float *out, float *um_out, float *skip_out, int N, int Cin, int H, int W,
+                                 float wscale, float skip_wscale, float xscale, void *stream) {
+    SLR_CHECK_ARG(z && mask && bias && out && um_out && skip_out, "null pointer");
+    SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
+    if (int e = check_xscale(xscale)) return e;
+    SLR_CHECK_ARG(wscale > 0.0f && skip_wscale > 0.0f, "wscale");
+    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && (H + 3) / 4 < 65536, "sizes");
+    hipLaunchKernelGGL(narrow_gather_kernel, dim3((W + 63) / 64, (H + 3) / 4, N), dim3(256), 0, (hipStream_t)stream, z, mask, bias, next_scale,
+                       next_shift, skip_bias, out, um_out, skip_out, H, W, (float)Cin, (float)Cin * 9.0f, 1.0f / (xscale * wscale),
+                       1.0f / (xscale * skip_wscale));
+    SLR_CHECK_LAUNCH();
+    return 0;
 }

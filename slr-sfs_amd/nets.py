@@ -48,6 +48,7 @@ class _Route(threading.local):
     winograd = False                     # ... its 3x3 convolutions as Winograd F(2x2, 3x3) (csrc/conv_wino.hpp); False (= FP32_WINOGRAD): direct
     fused_skips = True                   # a block's 1x1 skip convolution rides in its second 3x3 kernel (slr_*_forward_skip); staged_skips(): two kernels
     fused_pools = True                   # ... and a "Down" block's average pool in that kernel's epilogue; staged_skips(pools_only=True): pool kernel
+    narrow_tail = True                   # the 128 -> 3 block's first convolution and skip ride in the block before (slr_pconv3x3_forward_tail + slr_narrow_gather); staged_narrow_end(): the two-kernel path
 
 
 _S = _Route()
@@ -150,6 +151,19 @@ class staged_skips:
 
     def __exit__(self, *exc):
         _S.fused_skips, _S.fused_pools = self._prev
+        return False
+
+
+class staged_narrow_end:
+    """VALIDATION AID: inside, the decoder's last 128-channel block writes its result and the 128 -> 3 block reads it back with the
+    <= 4-channel kernel (slr_pconv3x3_forward -> slr_pconv3x3_forward_skipout) -- the two-kernel path the tail route is tested against
+    (tests/test_gpu_decoder_tail.py)."""
+
+    def __enter__(self):
+        self._prev, _S.narrow_tail = _S.narrow_tail, False
+
+    def __exit__(self, *exc):
+        _S.narrow_tail = self._prev
         return False
 
 
@@ -458,6 +472,41 @@ class PartialConv(Conv):
             layout, partial=True, skip_conv=skip_conv, skip_b8=skip_b8, pool=pool)
         return c.out, c.um
 
+    def _tail_weights(self, skip_conv):
+        """Column weights of the tail phase for THIS 128 -> 3 convolution and the block's 1x1 ``skip_conv`` (slr_conv_tail_weights), prepared
+        once per device / weight version: (buffer, wscale, skip wscale) -- each branch its own power of two, by _split_weights' rule."""
+        w, wb = self.weight, skip_conv.weight
+
+        def make():
+            def scale(t):
+                amax = float(t.abs().max())
+                return 2.0 ** math.floor(math.log2(4096.0 / amax)) if amax > 0 else 1.0
+            buf = torch.empty(_lib.lib().slr_conv_tail_weight_bytes(w.shape[1]), dtype=torch.uint8, device=w.device)
+            wscale, swscale = scale(w), scale(wb)
+            _lib.call("slr_conv_tail_weights", w.device, w, wb, buf, w.shape[1], wscale, swscale)
+            return buf, wscale, swscale
+        return _cached(self, "_wtail", make, w, wb)
+
+    def forward_tail(self, x, mask, residual, nxt):
+        """This block's second partial convolution (``x``: the activated output of the first, channel-blocked like ``residual``) WITHOUT its
+        result: the tail phase hands the next block ``nxt`` (128 -> 3, narrow form) what its first convolution and skip need, and the gather
+        finishes them (slr_pconv3x3_forward_tail, slr_narrow_gather; split-f16 rung).  Returns what ``nxt.conv_aa.forward_skipout`` returns
+        on the unwritten result: (activated input of nxt's second convolution, update mask, skip)."""
+        assert self.k == 3 and _fused_ok(x, mask, residual) and not _S.f32_kernels
+        N, cin, H, W = x.shape
+        cout = self.weight.shape[0]
+        buf, wscale, xscale, _ = self._split_weights()
+        tbuf, twscale, tswscale = nxt.conv_aa._tail_weights(nxt.conv_b)
+        tsc, tsh = nxt.bn1.scale_shift()
+        nsc, nsh = nxt.bn2.scale_shift()
+        z = torch.empty(N, 32, H, W, device=x.device, dtype=x.dtype)
+        um = torch.empty(N, 1, H, W, device=x.device, dtype=x.dtype)
+        _lib.call("slr_pconv3x3_forward_tail", x.device, x, mask, buf, wscale, xscale, self.bias, residual, tsc, tsh, tbuf, z, um,
+                  N, cin, cout, H, W)
+        a, m, skip = (torch.empty(N, c, H, W, device=x.device, dtype=x.dtype) for c in (3, 1, 3))
+        _lib.call("slr_narrow_gather", x.device, z, um, nxt.conv_aa.bias, nsc, nsh, None, a, m, skip, N, cout, H, W, twscale, tswscale, xscale)
+        return a, m, skip
+
     def forward(self, x, mask, residual=None, next_bn=None, pre_bn=None, layout=0):
         cin = x.shape[1]
         assert mask is not None or pre_bn is not None
@@ -552,6 +601,26 @@ class PconvResBlock(nn.Module):
         self.has_resample = bool(resample)
         self.pools = "Up" if resample == "Up" else bool(resample)        # the resampling the fused second convolution can take into its epilogue
 
+    def tail_route(self, nxt, x, mask, b8_in):
+        """Does this block run on ``x`` with the next block's (``nxt``) first convolution and skip folded into its second kernel?  This one:
+        128 -> 128 with the identity residual (staged form), channel-blocked, no resampling; ``nxt``: 128 -> 3 in the narrow form; the
+        split-f16 rung (either activation scale).  The fp32 and Winograd rungs, torch_convolutions() and staged_narrow_end() keep the
+        two-kernel path."""
+        if not (_S.narrow_tail and x.is_cuda and b8_in and mask is not None) or _S.f32_kernels or _S.torch_convs or _S.cpu_reference:
+            return False
+        if self.conv_b is not None or self.has_resample or tuple(self.conv_ab.weight.shape[:2]) != (128, 128):
+            return False
+        return (_block_route(self, x, b8_in).form == "staged" and nxt.conv_b is not None and nxt.conv_aa.weight.shape[0] == 3 and
+                nxt.conv_aa.weight.shape[1] == 128 and _block_route(nxt, x, True).form == "narrow")
+
+    def forward_with_narrow(self, nxt, x, mask):
+        """This block and ``nxt`` on the tail route (see tail_route): -> what ``nxt`` returns."""
+        r = _block_route(self, x, True)
+        a, m = self.conv_aa(x, mask, next_bn=self.bn2.scale_shift(), pre_bn=self.bn1.scale_shift(), layout=r.first)
+        a, m, skip = self.conv_ab.forward_tail(a, m, x, nxt)
+        a, m = nxt.conv_ab(a, m, residual=skip)
+        return nxt.resample(a, False), nxt.resample_mask(m), False
+
     def forward(self, x, mask, b8_in=False):
         """-> (y, update_mask, b8_out).  mask: None = (x != 0) per channel (architectures.py:369; x is NCHW then), else
         [N,1,H,W] channel-uniform; ``b8_in`` / ``b8_out``: x / y are channel-blocked in memory (see _b8)."""
@@ -620,12 +689,19 @@ class DecoderPconv2(nn.Module):
         ch = [cin] + _DEC + [cout]
         self.blocks = nn.ModuleList(PconvResBlock(ch[i], ch[i + 1], _UPDOWN[i]) for i in range(8))
 
-    def forward(self, x):
+    def forward(self, x, return_mask=False):
+        """``return_mask``: -> (frame, the last block's update mask [N,1,H,W]) (the tests compare routes on both)."""
         mask, b8 = None, False                           # (x != 0) per channel, derived inside the first block
-        for b in self.blocks:
-            x, mask, b8 = b(x, mask, b8)
+        blocks, i = self.blocks, 0
+        while i < len(blocks):
+            if i + 1 < len(blocks) and blocks[i].tail_route(blocks[i + 1], x, mask, b8):       # the narrow end rides in the block before it
+                x, mask, b8 = blocks[i].forward_with_narrow(blocks[i + 1], x, mask)
+                i += 2
+                continue
+            x, mask, b8 = blocks[i](x, mask, b8)
+            i += 1
         assert not b8                                    # the 1- / 3-channel end is NCHW
-        return x
+        return (x, mask) if return_mask else x
 
 
 class BGDecoder(nn.Module):
