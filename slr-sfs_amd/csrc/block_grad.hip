@@ -1,7 +1,10 @@
 // block_grad.hip -- what the decoder block needs to learn beyond its 3x3 convolutions (ABI 16): ResNet_Block_Pconv2 in training mode
 // (models/layers/blocks.py:218-248) with the noise-conditioned partial batch-norm of models/layers/normalization.py:19-52, 256-354.
-//   * batch statistics: per channel the sums of x and x^2 over ALL elements (normalization.py:325-329) in double, the count N H W or
-//     sum(mask) + eps; mean and var = m2 - m^2 formed in double and rounded once.
+// The batch-norm kernels are one family for both mask kinds: the channel-uniform plane mask of every block (or none) and the per-element
+// mask x != 0 of the decoder's first block (ABI 17, architectures.py:369; the rest of that block: csrc/decoder_grad.hip).
+//   * batch statistics: per channel the sums of x and x^2 over ALL elements (normalization.py:325-329) in double, the count N H W,
+//     sum(mask) + eps or, per channel, the integer number of nonzero elements + eps (normalization.py:319-335 with a [N,C,H,W] mask); mean
+//     and var = m2 - m^2 formed in double and rounded once.
 //   * training BN + ReLU + mask: a = relu(x * scale[n,c] - shift[n,c]) * mask with per-sample tables (gain and bias come from the noise).
 //   * its backward: one reduction pass (s0 = sum gy, s1 = sum gy x per (n, c), gy = ga * mask * [y > 0], the gate recomputed from x),
 //     a finalize kernel (dgain, dbias, the per-channel coefficients of the statistics' gradient) and one elementwise pass
@@ -17,66 +20,101 @@
 
 namespace slr {
 
+// ------------------------------------------------------------------ the two mask kinds
+// NZ = false: the channel-uniform plane `mask` [N,1,H,W], or none (NULL).  One count for all channels: N H W or sum(mask) + eps.
+// NZ = true:  k = [x != 0] per element, recomputed from x by every kernel as the ReLU gate is.  One count per channel: nnz + eps, an integer
+//             summed as one.  `mask` is NULL.
+// The two reduction kernels give a thread the PPT items of their mask kind before the one workgroup sum, so that the float64 wave
+// reductions are paid once per PPT items.
+constexpr int BN_PPT_PLANE = 1, BN_PPT_NONZERO = 8;
+constexpr int bn_ppt(bool nz) { return nz ? BN_PPT_NONZERO : BN_PPT_PLANE; }
+
 // ------------------------------------------------------------------ 1. batch statistics
-// part[(plane * GX + bx) * 2 KS + ...]: the workgroup's sums of x and x^2 per channel (KS = 8 channels blocked, 1 NCHW) in double;
-// mpart[n * GX + bx]: its sum of the mask, written by the workgroups of the first plane of every image.
-template <bool B8>
+// part[(plane * GX + bx) * 2 KS + ...]: the workgroup's sums of x and x^2 per channel (KS = 8 channels blocked, 1 NCHW) in double -- over all
+// elements, which with NZ is over the kept ones: the others are exact zeros.  What the count is made of goes to `cnt`:
+//   plane:   mpart[n * GX + bx], the workgroup's sum of the mask in double, written by the workgroups of the first plane of every image;
+//   nonzero: cpart[(plane * GX + bx) * KS + ...], its number of nonzero elements per channel.
+template <bool B8, bool NZ, int PPT>
 __global__ __launch_bounds__(BG_THREADS) void bn_stats_kernel(const float *__restrict__ x, const float *__restrict__ mask,
-                                                             double *__restrict__ part, double *__restrict__ mpart, int planes, int HW,
+                                                             double *__restrict__ part, void *__restrict__ cnt, int planes, int HW,
                                                              int vec) {
-    constexpr int K = BgItem<B8>::K, KS = B8 ? 8 : 1, NV = 2 * KS + 1;
+    constexpr int K = BgItem<B8>::K, KS = B8 ? 8 : 1, NV = 2 * KS + (NZ ? 0 : 1);
     __shared__ double red[NV][BG_THREADS / 64];
-    const BgItem<B8> it = bg_item<B8>(planes, HW, vec);
-    float e[K];
-    bg_load<B8>(it, x, e);
+    const int plane = blockIdx.y, n = plane / planes;    // (bg_item's own division)
+    const bool msum = !NZ && mask && plane == n * planes;            // (uniform over the workgroup)
     double v[NV];
+    unsigned c[KS];
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = 0.0;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double d = (double)e[k];
-        v[B8 ? 2 * k : 0] += d;
-        v[B8 ? 2 * k + 1 : 1] += d * d;
-    }
-    const bool msum = mask && it.c0 == 0;                // (uniform over the workgroup)
-    if (msum) {
-        float m[K];
-        bg_mask<B8>(it, mask, m);
-        if (B8) v[2 * KS] = (double)m[0];
-        else
+    for (int j = 0; j < KS; ++j) c[j] = 0;
+    auto item = [&](int j) {
+        const BgItem<B8> it = bg_item<B8, PPT>(planes, HW, vec, j);
+        if (PPT > 1 && it.cnt == 0) return false;        // (a thread's only item stays: it reads as zeros, as it always did)
+        float e[K];
+        bg_load<B8>(it, x, e);                           // (elements past the plane read as 0: no sum and no count sees them)
 #pragma unroll
-            for (int k = 0; k < K; ++k) v[2 * KS] += (double)m[k];
-    }
+        for (int k = 0; k < K; ++k) {
+            const double d = (double)e[k];
+            v[B8 ? 2 * k : 0] += d;
+            v[B8 ? 2 * k + 1 : 1] += d * d;
+            if (NZ) c[B8 ? k : 0] += e[k] != 0.0f ? 1u : 0u;
+        }
+        if (msum) {
+            float m[K];
+            bg_mask<B8>(it, mask, m);
+            if (B8) v[NV - 1] = j == 0 ? (double)m[0] : v[NV - 1] + (double)m[0];       // (the first item starts the sum: a -0.0 stays one)
+            else
+#pragma unroll
+                for (int k = 0; k < K; ++k) v[NV - 1] += (double)m[k];
+        }
+        return true;
+    };
+    bg_items<PPT>(item);
     block_sum<NV, BG_THREADS / 64>(v, red);
+    if constexpr (NZ) {
+        __shared__ unsigned cred[KS][BG_THREADS / 64];
+        block_count<KS, BG_THREADS / 64>(c, cred);
+    }
     if (threadIdx.x == 0) {
-        double *p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (2 * KS);
+        const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        double *p = part + wg * (2 * KS);
 #pragma unroll
         for (int j = 0; j < 2 * KS; ++j) p[j] = v[j];
-        if (msum) mpart[(size_t)it.n * gridDim.x + blockIdx.x] = v[2 * KS];
+        if constexpr (NZ)
+#pragma unroll
+            for (int j = 0; j < KS; ++j) ((unsigned *)cnt)[wg * KS + j] = c[j];
+        else if (msum) ((double *)cnt)[(size_t)n * gridDim.x + blockIdx.x] = v[NV - 1];
     }
 }
 
-// One workgroup per channel: the partial sums in the order (n, bx); mean, var (and the count, by channel 0).
+// One workgroup per channel: the partial sums in the order (n, bx); mean, var and the count: nnz + eps of the channel (cpart; integers
+// below 2^31, every sum of them exact in double), sum(mask) + eps (mpart) or N H W (neither), the last two written by channel 0 alone.
 __global__ __launch_bounds__(256) void bn_stats_final_kernel(const double *__restrict__ part, const double *__restrict__ mpart,
-                                                             float *__restrict__ mean, float *__restrict__ var, float *__restrict__ cnt_out,
-                                                             int N, int C, int GX, int b8, int has_mask, float eps, int HW) {
+                                                             const unsigned *__restrict__ cpart, float *__restrict__ mean,
+                                                             float *__restrict__ var, float *__restrict__ count, int N, int C, int GX,
+                                                             int b8, float eps, int HW) {
     __shared__ double red[3][4];
     const int c = blockIdx.x;
     double v[3] = {0.0, 0.0, 0.0};
+    unsigned long long nz = 0;
     for (int i = threadIdx.x; i < N * GX; i += 256) {
         const int n = i / GX, bx = i - n * GX;
         const double *q = bg_part(part, n, c, bx, C, GX, b8);
         v[0] += q[0];
         v[1] += q[1];
-        if (has_mask) v[2] += mpart[i];
+        if (cpart) nz += bg_cpart(cpart, n, c, bx, C, GX, b8);
+        else if (mpart) v[2] += mpart[i];
     }
+    if (cpart) v[2] = (double)nz;
     block_sum<3, 4>(v, red);
     if (threadIdx.x == 0) {
-        const double cnt = has_mask ? v[2] + (double)eps : (double)N * (double)HW;       // normalization.py:325 / torch.mean
+        const double cnt = cpart || mpart ? v[2] + (double)eps : (double)N * (double)HW;       // normalization.py:325 / torch.mean
         const double m = v[0] / cnt;
         mean[c] = (float)m;
         var[c] = (float)(v[1] / cnt - m * m);
-        if (c == 0) cnt_out[0] = (float)cnt;
+        if (cpart) count[c] = (float)cnt;
+        else if (c == 0) count[0] = (float)cnt;
     }
 }
 
@@ -96,7 +134,7 @@ __global__ __launch_bounds__(256) void bn_tables_kernel(const float *__restrict_
     shift[i] = bias ? sh - bias[i] : sh;
 }
 
-template <bool B8>
+template <bool B8, bool NZ>
 __global__ __launch_bounds__(BG_THREADS) void bn_train_forward_kernel(const float *__restrict__ x, const float *__restrict__ scale,
                                                                      const float *__restrict__ shift, const float *__restrict__ mask,
                                                                      float *__restrict__ a, int planes, int HW, int vec) {
@@ -108,19 +146,20 @@ __global__ __launch_bounds__(BG_THREADS) void bn_train_forward_kernel(const floa
     bg_load<B8>(it, x, e);
     bg_table<B8>(it, scale, it.n, C, sc);
     bg_table<B8>(it, shift, it.n, C, sh);
-    bg_mask<B8>(it, mask, m);
+    if (!NZ) bg_mask<B8>(it, mask, m);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
+        if (NZ) m[k] = e[k] != 0.0f ? 1.0f : 0.0f;
         const float r = relu_nan(e[k] * sc[k] - sh[k]);  // (a NaN pre-activation stays one, as torch.relu's)
-        e[k] = mask ? r * m[k] : r;
+        e[k] = NZ || mask ? r * m[k] : r;
     }
     bg_store<B8>(it, a, e);
 }
 
 // ------------------------------------------------------------------ 3. its backward
-// gy = ga * mask * [not x * scale - shift <= 0] at the thread's elements (the forward's own fp32 expression decides the gate; a NaN
-// pre-activation leaves it open, as torch's ReLU backward does)
-template <bool B8>
+// gy = ga * mask * [not x * scale - shift <= 0] at the item's elements (the forward's own fp32 expression decides the gate; a NaN
+// pre-activation leaves it open, as torch's ReLU backward does).  Elements past the plane get 0: ga and x read as 0 there.
+template <bool B8, bool NZ>
 __device__ __forceinline__ void bg_gate(const BgItem<B8> &it, const float *__restrict__ ga, const float *__restrict__ mask,
                                         const float *__restrict__ scale, const float *__restrict__ shift, int C,
                                         const float (&e)[BgItem<B8>::K], float (&sc)[BgItem<B8>::K], float (&gy)[BgItem<B8>::K]) {
@@ -129,40 +168,45 @@ __device__ __forceinline__ void bg_gate(const BgItem<B8> &it, const float *__res
     bg_load<B8>(it, ga, g);
     bg_table<B8>(it, scale, it.n, C, sc);
     bg_table<B8>(it, shift, it.n, C, sh);
-    bg_mask<B8>(it, mask, m);
+    if (!NZ) bg_mask<B8>(it, mask, m);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const float y = e[k] * sc[k] - sh[k];
-        const float gm = mask ? g[k] * m[k] : g[k];
-        gy[k] = y <= 0.0f ? 0.0f : gm;                   // torch's ReLU backward closes on `<= 0` only: a NaN pre-activation passes gm
+        // torch's ReLU backward closes on `<= 0` only: a NaN pre-activation passes the gradient.  The plane mask is a factor (a NaN
+        // gradient under a zero mask stays NaN, as autograd's product); the nonzero mask is a second gate.
+        if (NZ) gy[k] = (y <= 0.0f || e[k] == 0.0f) ? 0.0f : g[k];
+        else gy[k] = y <= 0.0f ? 0.0f : mask ? g[k] * m[k] : g[k];
     }
 }
 
 // part[(plane * GX + bx) * 2 KS + ...] = the workgroup's s0 = sum gy and s1 = sum gy * x per channel, in double
-template <bool B8>
+template <bool B8, bool NZ, int PPT>
 __global__ __launch_bounds__(BG_THREADS) void bn_backward_reduce_kernel(const float *__restrict__ x, const float *__restrict__ ga,
                                                                        const float *__restrict__ mask, const float *__restrict__ scale,
                                                                        const float *__restrict__ shift, double *__restrict__ part,
                                                                        int planes, int HW, int vec) {
     constexpr int K = BgItem<B8>::K, KS = B8 ? 8 : 1, NV = 2 * KS;
     __shared__ double red[NV][BG_THREADS / 64];
-    const BgItem<B8> it = bg_item<B8>(planes, HW, vec);
     const int C = B8 ? planes * 8 : planes;
-    float e[K], sc[K], gy[K];
     double v[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = 0.0;
-    bg_load<B8>(it, x, e);
-    if (it.cnt) {
-        bg_gate<B8>(it, ga, mask, scale, shift, C, e, sc, gy);
+    auto item = [&](int j) {
+        const BgItem<B8> it = bg_item<B8, PPT>(planes, HW, vec, j);
+        float e[K], sc[K], gy[K];
+        bg_load<B8>(it, x, e);
+        if (it.cnt) {
+            bg_gate<B8, NZ>(it, ga, mask, scale, shift, C, e, sc, gy);
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const bool in = B8 || k < it.cnt;
-            const double d = in ? (double)gy[k] : 0.0;
-            v[B8 ? 2 * k : 0] += d;
-            v[B8 ? 2 * k + 1 : 1] += d * (double)e[k];
+            for (int k = 0; k < K; ++k) {
+                const double d = B8 || k < it.cnt ? (double)gy[k] : 0.0;   // (gy past the plane is 0 as it is)
+                v[B8 ? 2 * k : 0] += d;
+                v[B8 ? 2 * k + 1 : 1] += d * (double)e[k];
+            }
         }
-    }
+        return it.cnt != 0;
+    };
+    bg_items<PPT>(item);
     block_sum<NV, BG_THREADS / 64>(v, red);
     if (threadIdx.x == 0) {
         double *p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NV;
@@ -172,13 +216,13 @@ __global__ __launch_bounds__(BG_THREADS) void bn_backward_reduce_kernel(const fl
 }
 
 // One workgroup per channel, the images in order: (s0, s1)[n] = the partial sums in bx order; dbias[n,c] = s0, dgain[n,c] = rs (s1 - m s0);
-// P = sum_n gain s0, Q = sum_n gain s1, dv = -rs^3 (Q - m P) / 2 and
+// P = sum_n gain s0, Q = sum_n gain s1, dv = -rs^3 (Q - m P) / 2 and, with the count cnt[c * cstride] (one for all channels: stride 0),
 //     ab[c] = A = -rs P / cnt,  ab[C + c] = B = 2 dv / cnt     (dx = gy * scale + A + B (x - m); stored statistics: A = B = 0).
 __global__ __launch_bounds__(256) void bn_backward_final_kernel(const double *__restrict__ part, const float *__restrict__ mean,
                                                                 const float *__restrict__ var, const float *__restrict__ gain,
-                                                                const float *__restrict__ cnt, float eps, float *__restrict__ dgain,
-                                                                float *__restrict__ dbias, float *__restrict__ ab, int N, int C, int GX,
-                                                                int b8, int stored) {
+                                                                const float *__restrict__ cnt, int cstride, float eps,
+                                                                float *__restrict__ dgain, float *__restrict__ dbias,
+                                                                float *__restrict__ ab, int N, int C, int GX, int b8, int stored) {
     __shared__ double red[2][4];
     const int c = blockIdx.x;
     const double m = (double)mean[c], rs = 1.0 / sqrt((double)var[c] + (double)eps);
@@ -201,15 +245,16 @@ __global__ __launch_bounds__(256) void bn_backward_final_kernel(const double *__
         __syncthreads();                                 // (red is free again)
     }
     if (threadIdx.x == 0 && ab) {
-        const double n_el = (double)cnt[0];
+        const double n_el = stored ? 1.0 : (double)cnt[(size_t)c * cstride];       // (stored statistics come without a count)
         const double dv = -0.5 * rs * rs * rs * (Q - m * P);
         ab[c] = stored ? 0.0f : (float)(-rs * P / n_el);
         ab[C + c] = stored ? 0.0f : (float)(2.0 * dv / n_el);
     }
 }
 
-// dx = gy * scale + (A + B * (x - mean)) (+ addend);  ab = NULL: stored statistics, dx = gy * scale (+ addend)
-template <bool B8>
+// dx = gy * scale + (A + B * (x - mean)) (+ addend) at EVERY element, those the mask drops included: the statistics' gradient reaches them
+// as the reference's autograd does.  ab = NULL: stored statistics, dx = gy * scale (+ addend)
+template <bool B8, bool NZ>
 __global__ __launch_bounds__(BG_THREADS) void bn_backward_dx_kernel(const float *__restrict__ x, const float *__restrict__ ga,
                                                                    const float *__restrict__ mask, const float *__restrict__ scale,
                                                                    const float *__restrict__ shift, const float *__restrict__ mean,
@@ -221,7 +266,7 @@ __global__ __launch_bounds__(BG_THREADS) void bn_backward_dx_kernel(const float 
     const int C = B8 ? planes * 8 : planes;
     float e[K], sc[K], gy[K], o[K];
     bg_load<B8>(it, x, e);
-    bg_gate<B8>(it, ga, mask, scale, shift, C, e, sc, gy);
+    bg_gate<B8, NZ>(it, ga, mask, scale, shift, C, e, sc, gy);
 #pragma unroll
     for (int k = 0; k < K; ++k) o[k] = gy[k] * sc[k];
     if (ab) {
@@ -572,20 +617,107 @@ __global__ __launch_bounds__(256) void upsample2x_backward_b8_kernel(const float
 }
 
 // ------------------------------------------------------------------ host side
-static bool bg_sizes_ok(int N, int C, int H, int W) {
-    return N > 0 && C > 0 && H > 0 && W > 0 && (long long)N * C * H * W < (1LL << 31) - 4 * BG_THREADS && (long long)N * C <= 65535;       // (a thread's first pixel, rounded up to a workgroup of 4-pixel items, stays an int)
+// The workspace of a mask kind: part | mpart or cpart | ab -- the partial sums (the blocked form's count; the NCHW form needs no more),
+// the mask's partial sums [N][GX] in double or the nonzero counts [N][C][GX], the statistics' coefficients.
+static size_t bn_part_bytes(int N, int C, int HW, bool nz) { return al256((size_t)N * C * bg_gx(HW, true, bn_ppt(nz)) * 2 * sizeof(double)); }
+static size_t bn_cnt_bytes(int N, int C, int HW, bool nz) {
+    return nz ? al256((size_t)N * C * bg_gx(HW, true, bn_ppt(nz)) * sizeof(unsigned)) : al256((size_t)N * bg_gx(HW, true, bn_ppt(nz)) * sizeof(double));
 }
-static int bg_gx(int HW, bool b8) { return b8 ? (HW + BG_THREADS - 1) / BG_THREADS : (HW + 4 * BG_THREADS - 1) / (4 * BG_THREADS); }
-// the partial sums (the blocked form's count; the NCHW form needs a quarter), the mask's partial sums, the statistics' coefficients
-static size_t bg_part_bytes(int N, int C, int H, int W) { return al256((size_t)N * C * bg_gx(H * W, true) * 2 * sizeof(double)); }
-static size_t bg_mpart_bytes(int N, int H, int W) { return al256((size_t)N * bg_gx(H * W, true) * sizeof(double)); }
-static size_t bg_ws_bytes(int N, int C, int H, int W) {
-    return bg_part_bytes(N, C, H, W) + bg_mpart_bytes(N, H, W) + al256((size_t)2 * C * sizeof(float));
+static size_t bn_ws_bytes(int N, int C, int HW, bool nz) {
+    return bn_part_bytes(N, C, HW, nz) + bn_cnt_bytes(N, C, HW, nz) + al256((size_t)2 * C * sizeof(float));
 }
-static bool bg_ws_ok(const void *ws, size_t ws_bytes, int N, int C, int H, int W) {
-    return ws && !((uintptr_t)ws & 255) && ws_bytes >= bg_ws_bytes(N, C, H, W);
+
+// An export of the family: its name and its workspace function's (for the error texts), its mask kind
+struct BnExport {
+    const char *fn, *ws_fn;
+    bool nz;
+};
+static int bn_ws_check(const BnExport &ex, const void *ws, size_t ws_bytes, int N, int C, int HW) {
+    if (ws && !((uintptr_t)ws & 255) && ws_bytes >= bn_ws_bytes(N, C, HW, ex.nz)) return 0;
+    set_error("%s: ws: %s(N, C, H, W) bytes, 256-byte aligned", ex.fn, ex.ws_fn);
+    return SLR_E_WORKSPACE;
 }
-static dim3 bg_grid(int N, int C, int HW, bool b8) { return dim3(bg_gx(HW, b8), b8 ? N * (C / 8) : N * C); }
+
+// Launches the instantiation of a family kernel for (b8, ex.nz); KERNEL: one of the BN_* macros below, which add the PPT of the mask kind
+#define BN_LAUNCH(KERNEL, grid, ...)                                                                                    \
+    do {                                                                                                                \
+        if (b8 && ex.nz) hipLaunchKernelGGL((KERNEL(true, true)), grid, dim3(BG_THREADS), 0, st, __VA_ARGS__);          \
+        else if (b8) hipLaunchKernelGGL((KERNEL(true, false)), grid, dim3(BG_THREADS), 0, st, __VA_ARGS__);             \
+        else if (ex.nz) hipLaunchKernelGGL((KERNEL(false, true)), grid, dim3(BG_THREADS), 0, st, __VA_ARGS__);          \
+        else hipLaunchKernelGGL((KERNEL(false, false)), grid, dim3(BG_THREADS), 0, st, __VA_ARGS__);                    \
+        SLR_CHECK_HIP_FN(ex.fn, hipGetLastError());                                                                     \
+    } while (0)
+#define BN_STATS(B8, NZ) bn_stats_kernel<B8, NZ, bn_ppt(NZ)>
+#define BN_FORWARD(B8, NZ) bn_train_forward_kernel<B8, NZ>
+#define BN_REDUCE(B8, NZ) bn_backward_reduce_kernel<B8, NZ, bn_ppt(NZ)>
+#define BN_DX(B8, NZ) bn_backward_dx_kernel<B8, NZ>
+
+static int bn_stats(const BnExport &ex, const float *x, const float *mask, float eps, float *mean, float *var, float *count, int N, int C,
+                    int H, int W, int b8, void *ws, size_t ws_bytes, void *stream) {
+    SLR_CHECK_ARG_FN(ex.fn, x && mean && var && count, "null pointer");
+    BG_CHECK_PLANES(ex.fn, C);
+    SLR_CHECK_ARG_FN(ex.fn, eps >= 0.0f, "eps");
+    SLR_CHECK_ARG_FN(ex.fn, !(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)count) & 3), "4-byte aligned tensors");
+    SLR_CHECK_ARG_FN(ex.fn, !(b8 && ((uintptr_t)x & 15)), "16-byte aligned channel-blocked tensors");
+    const int HW = H * W;
+    if (const int e = bn_ws_check(ex, ws, ws_bytes, N, C, HW)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)mask) & 15);
+    double *part = (double *)ws;
+    void *cnt = (char *)ws + bn_part_bytes(N, C, HW, ex.nz);
+    const dim3 grid = bg_grid(N, C, HW, b8, bn_ppt(ex.nz));
+    BN_LAUNCH(BN_STATS, grid, x, mask, part, cnt, b8 ? C / 8 : C, HW, vec);
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, st, (const double *)part, (const double *)(!ex.nz && mask ? cnt : nullptr),
+                       (const unsigned *)(ex.nz ? cnt : nullptr), mean, var, count, N, C, (int)grid.x, b8, eps, HW);
+    SLR_CHECK_HIP_FN(ex.fn, hipGetLastError());
+    return 0;
+}
+
+static int bn_forward(const BnExport &ex, const float *x, const float *scale, const float *shift, const float *mask, float *a, int N, int C,
+                      int H, int W, int b8, void *stream) {
+    SLR_CHECK_ARG_FN(ex.fn, x && scale && shift && a, "null pointer");
+    BG_CHECK_PLANES(ex.fn, C);
+    SLR_CHECK_ARG_FN(ex.fn, !(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)a | (uintptr_t)scale | (uintptr_t)shift) & 3), "4-byte aligned tensors");
+    SLR_CHECK_ARG_FN(ex.fn, !(b8 && (((uintptr_t)x | (uintptr_t)a) & 15)), "16-byte aligned channel-blocked tensors");
+    const int HW = H * W, vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)a) & 15);
+    hipStream_t st = (hipStream_t)stream;
+    BN_LAUNCH(BN_FORWARD, bg_grid(N, C, HW, b8), x, scale, shift, mask, a, b8 ? C / 8 : C, HW, vec);
+    return 0;
+}
+
+static int bn_backward(const BnExport &ex, const float *x, const float *ga, const float *mask, const float *scale, const float *shift,
+                       const float *mean, const float *var, const float *gain, const float *count, float eps, const float *addend, float *dx,
+                       float *dgain, float *dbias, int stored, int N, int C, int H, int W, int b8, void *ws, size_t ws_bytes, void *stream) {
+    SLR_CHECK_ARG_FN(ex.fn, x && ga && scale && shift && mean && var, "null pointer");
+    SLR_CHECK_ARG_FN(ex.fn, dx || dgain || dbias, "null pointer: nothing to compute");
+    SLR_CHECK_ARG_FN(ex.fn, stored == 0 || stored == 1, "stored");
+    SLR_CHECK_ARG_FN(ex.fn, stored || count, ex.nz ? "null pointer: batch statistics need their counts" : "null pointer: batch statistics need their count");
+    SLR_CHECK_ARG_FN(ex.fn, !addend || dx, "addend goes with dx");
+    BG_CHECK_PLANES(ex.fn, C);
+    SLR_CHECK_ARG_FN(ex.fn, eps >= 0.0f, "eps");
+    SLR_CHECK_ARG_FN(ex.fn, !(((uintptr_t)x | (uintptr_t)ga | (uintptr_t)mask | (uintptr_t)addend | (uintptr_t)dx | (uintptr_t)dgain | (uintptr_t)dbias) & 3),
+                     "4-byte aligned tensors");
+    SLR_CHECK_ARG_FN(ex.fn, !(b8 && (((uintptr_t)x | (uintptr_t)ga | (uintptr_t)addend | (uintptr_t)dx) & 15)), "16-byte aligned channel-blocked tensors");
+    const int HW = H * W;
+    const bool reduce = dgain || dbias || !stored;
+    if (reduce)
+        if (const int e = bn_ws_check(ex, ws, ws_bytes, N, C, HW)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)ga | (uintptr_t)mask | (uintptr_t)addend | (uintptr_t)dx) & 15);
+    const int planes = b8 ? C / 8 : C;
+    float *ab = nullptr;
+    if (reduce) {
+        double *part = (double *)ws;
+        if (dx && !stored) ab = (float *)((char *)ws + bn_part_bytes(N, C, HW, ex.nz) + bn_cnt_bytes(N, C, HW, ex.nz));
+        const dim3 grid = bg_grid(N, C, HW, b8, bn_ppt(ex.nz));
+        BN_LAUNCH(BN_REDUCE, grid, x, ga, mask, scale, shift, part, planes, HW, vec);
+        hipLaunchKernelGGL(bn_backward_final_kernel, dim3(C), dim3(256), 0, st, (const double *)part, mean, var, gain, count, ex.nz ? 1 : 0, eps,
+                           dgain, dbias, ab, N, C, (int)grid.x, b8, stored);
+        SLR_CHECK_HIP_FN(ex.fn, hipGetLastError());
+    }
+    if (dx) BN_LAUNCH(BN_DX, bg_grid(N, C, HW, b8), x, ga, mask, scale, shift, mean, (const float *)ab, addend, dx, planes, HW, vec);
+    return 0;
+}
 
 static long long w1_chunks(int N, int HW) { return (long long)N * ((HW + W1_P - 1) / W1_P); }
 static int w1_tiles(int Cin, int Cout) { return ((Cin + W1_CI - 1) / W1_CI) * ((Cout + W1_CO - 1) / W1_CO); }
@@ -604,40 +736,23 @@ static int w1_splits(int N, int Cin, int Cout, int H, int W, int splits) {
 
 using namespace slr;
 
-#define BG_CHECK_PLANES(C)                                                                                              \
-    SLR_CHECK_ARG(bg_sizes_ok(N, C, H, W), "sizes (N * C * H * W < 2^31 - 1024, N * C <= 65535)");                             \
-    SLR_CHECK_ARG(b8 == 0 || b8 == 1, "b8");                                                                            \
-    SLR_CHECK_ARG(!b8 || C % 8 == 0, "a channel-blocked layout needs C % 8 == 0")
-
 // ------------------------------------------------------------------ C ABI
+// The batch-norm family's exports, plane mask (ABI 16) and nonzero mask (ABI 17): the arguments of the launchers above.
+static const BnExport BN_PLANE_STATS = {"slr_bn_batch_stats", "slr_bn_train_ws_bytes", false}, BN_PLANE_FORWARD = {"slr_bn_relu_mask_train", "slr_bn_train_ws_bytes", false},
+                      BN_PLANE_BACKWARD = {"slr_bn_relu_mask_backward", "slr_bn_train_ws_bytes", false},
+                      BN_NZ_STATS = {"slr_bn_nonzero_stats", "slr_bn_nonzero_ws_bytes", true}, BN_NZ_FORWARD = {"slr_bn_relu_nonzero_train", "slr_bn_nonzero_ws_bytes", true},
+                      BN_NZ_BACKWARD = {"slr_bn_relu_nonzero_backward", "slr_bn_nonzero_ws_bytes", true};
 
-SLR_EXPORT size_t slr_bn_train_ws_bytes(int N, int C, int H, int W) {
-    if (!bg_sizes_ok(N, C, H, W)) return 0;
-    return bg_ws_bytes(N, C, H, W);
-}
+SLR_EXPORT size_t slr_bn_train_ws_bytes(int N, int C, int H, int W) { return bg_sizes_ok(N, C, H, W) ? bn_ws_bytes(N, C, H * W, false) : 0; }
+SLR_EXPORT size_t slr_bn_nonzero_ws_bytes(int N, int C, int H, int W) { return bg_sizes_ok(N, C, H, W) ? bn_ws_bytes(N, C, H * W, true) : 0; }
 
 SLR_EXPORT int slr_bn_batch_stats(const float *x, const float *mask, float eps, float *mean, float *var, float *count, int N, int C, int H,
                                   int W, int b8, void *ws, size_t ws_bytes, void *stream) {
-    SLR_CHECK_ARG(x && mean && var && count, "null pointer");
-    BG_CHECK_PLANES(C);
-    SLR_CHECK_ARG(eps >= 0.0f, "eps");
-    SLR_CHECK_ARG(!(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)count) & 3), "4-byte aligned tensors");
-    SLR_CHECK_ARG(!(b8 && ((uintptr_t)x & 15)), "16-byte aligned channel-blocked tensors");
-    if (!bg_ws_ok(ws, ws_bytes, N, C, H, W)) {
-        set_error("%s: ws: slr_bn_train_ws_bytes(N, C, H, W) bytes, 256-byte aligned", __func__);
-        return SLR_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int HW = H * W, vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)mask) & 15);
-    double *part = (double *)ws, *mpart = (double *)((char *)ws + bg_part_bytes(N, C, H, W));
-    const dim3 grid = bg_grid(N, C, HW, b8);
-    if (b8) hipLaunchKernelGGL(bn_stats_kernel<true>, grid, dim3(BG_THREADS), 0, st, x, mask, part, mpart, C / 8, HW, vec);
-    else hipLaunchKernelGGL(bn_stats_kernel<false>, grid, dim3(BG_THREADS), 0, st, x, mask, part, mpart, C, HW, vec);
-    SLR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, st, (const double *)part, (const double *)mpart, mean, var, count, N, C,
-                       (int)grid.x, b8, mask ? 1 : 0, eps, HW);
-    SLR_CHECK_LAUNCH();
-    return 0;
+    return bn_stats(BN_PLANE_STATS, x, mask, eps, mean, var, count, N, C, H, W, b8, ws, ws_bytes, stream);
+}
+SLR_EXPORT int slr_bn_nonzero_stats(const float *x, float eps, float *mean, float *var, float *count, int N, int C, int H, int W, int b8,
+                                    void *ws, size_t ws_bytes, void *stream) {
+    return bn_stats(BN_NZ_STATS, x, nullptr, eps, mean, var, count, N, C, H, W, b8, ws, ws_bytes, stream);
 }
 
 SLR_EXPORT int slr_bn_train_tables(const float *mean, const float *var, const float *gain, const float *bias, float eps, float *scale,
@@ -653,60 +768,26 @@ SLR_EXPORT int slr_bn_train_tables(const float *mean, const float *var, const fl
 
 SLR_EXPORT int slr_bn_relu_mask_train(const float *x, const float *scale, const float *shift, const float *mask, float *a, int N, int C,
                                       int H, int W, int b8, void *stream) {
-    SLR_CHECK_ARG(x && scale && shift && a, "null pointer");
-    BG_CHECK_PLANES(C);
-    SLR_CHECK_ARG(!(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)a | (uintptr_t)scale | (uintptr_t)shift) & 3), "4-byte aligned tensors");
-    SLR_CHECK_ARG(!(b8 && (((uintptr_t)x | (uintptr_t)a) & 15)), "16-byte aligned channel-blocked tensors");
-    const int HW = H * W, vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)mask | (uintptr_t)a) & 15);
-    const dim3 grid = bg_grid(N, C, HW, b8);
-    hipStream_t st = (hipStream_t)stream;
-    if (b8) hipLaunchKernelGGL(bn_train_forward_kernel<true>, grid, dim3(BG_THREADS), 0, st, x, scale, shift, mask, a, C / 8, HW, vec);
-    else hipLaunchKernelGGL(bn_train_forward_kernel<false>, grid, dim3(BG_THREADS), 0, st, x, scale, shift, mask, a, C, HW, vec);
-    SLR_CHECK_LAUNCH();
-    return 0;
+    return bn_forward(BN_PLANE_FORWARD, x, scale, shift, mask, a, N, C, H, W, b8, stream);
+}
+SLR_EXPORT int slr_bn_relu_nonzero_train(const float *x, const float *scale, const float *shift, float *a, int N, int C, int H, int W,
+                                         int b8, void *stream) {
+    return bn_forward(BN_NZ_FORWARD, x, scale, shift, nullptr, a, N, C, H, W, b8, stream);
 }
 
 SLR_EXPORT int slr_bn_relu_mask_backward(const float *x, const float *ga, const float *mask, const float *scale, const float *shift,
                                          const float *mean, const float *var, const float *gain, const float *count, float eps,
                                          const float *addend, float *dx, float *dgain, float *dbias, int stored, int N, int C, int H, int W,
                                          int b8, void *ws, size_t ws_bytes, void *stream) {
-    SLR_CHECK_ARG(x && ga && scale && shift && mean && var, "null pointer");
-    SLR_CHECK_ARG(dx || dgain || dbias, "null pointer: nothing to compute");
-    SLR_CHECK_ARG(stored == 0 || stored == 1, "stored");
-    SLR_CHECK_ARG(stored || count, "null pointer: batch statistics need their count");
-    SLR_CHECK_ARG(!addend || dx, "addend goes with dx");
-    BG_CHECK_PLANES(C);
-    SLR_CHECK_ARG(eps >= 0.0f, "eps");
-    SLR_CHECK_ARG(!(((uintptr_t)x | (uintptr_t)ga | (uintptr_t)mask | (uintptr_t)addend | (uintptr_t)dx | (uintptr_t)dgain | (uintptr_t)dbias) & 3),
-                  "4-byte aligned tensors");
-    SLR_CHECK_ARG(!(b8 && (((uintptr_t)x | (uintptr_t)ga | (uintptr_t)addend | (uintptr_t)dx) & 15)), "16-byte aligned channel-blocked tensors");
-    const bool reduce = dgain || dbias || !stored;
-    if (reduce && !bg_ws_ok(ws, ws_bytes, N, C, H, W)) {
-        set_error("%s: ws: slr_bn_train_ws_bytes(N, C, H, W) bytes, 256-byte aligned", __func__);
-        return SLR_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int HW = H * W;
-    const int vec = HW % 4 == 0 && !(((uintptr_t)x | (uintptr_t)ga | (uintptr_t)mask | (uintptr_t)addend | (uintptr_t)dx) & 15);
-    const dim3 grid = bg_grid(N, C, HW, b8);
-    const int planes = b8 ? C / 8 : C;
-    float *ab = nullptr;
-    if (reduce) {
-        double *part = (double *)ws;
-        if (dx && !stored) ab = (float *)((char *)ws + bg_part_bytes(N, C, H, W) + bg_mpart_bytes(N, H, W));
-        if (b8) hipLaunchKernelGGL(bn_backward_reduce_kernel<true>, grid, dim3(BG_THREADS), 0, st, x, ga, mask, scale, shift, part, planes, HW, vec);
-        else hipLaunchKernelGGL(bn_backward_reduce_kernel<false>, grid, dim3(BG_THREADS), 0, st, x, ga, mask, scale, shift, part, planes, HW, vec);
-        SLR_CHECK_LAUNCH();
-        hipLaunchKernelGGL(bn_backward_final_kernel, dim3(C), dim3(256), 0, st, (const double *)part, mean, var, gain, count, eps, dgain,
-                           dbias, ab, N, C, (int)grid.x, b8, stored);
-        SLR_CHECK_LAUNCH();
-    }
-    if (dx) {
-        if (b8) hipLaunchKernelGGL(bn_backward_dx_kernel<true>, grid, dim3(BG_THREADS), 0, st, x, ga, mask, scale, shift, mean, (const float *)ab, addend, dx, planes, HW, vec);
-        else hipLaunchKernelGGL(bn_backward_dx_kernel<false>, grid, dim3(BG_THREADS), 0, st, x, ga, mask, scale, shift, mean, (const float *)ab, addend, dx, planes, HW, vec);
-        SLR_CHECK_LAUNCH();
-    }
-    return 0;
+    return bn_backward(BN_PLANE_BACKWARD, x, ga, mask, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias, stored, N, C, H, W, b8,
+                       ws, ws_bytes, stream);
+}
+SLR_EXPORT int slr_bn_relu_nonzero_backward(const float *x, const float *ga, const float *scale, const float *shift, const float *mean,
+                                            const float *var, const float *gain, const float *count, float eps, const float *addend,
+                                            float *dx, float *dgain, float *dbias, int stored, int N, int C, int H, int W, int b8, void *ws,
+                                            size_t ws_bytes, void *stream) {
+    return bn_backward(BN_NZ_BACKWARD, x, ga, nullptr, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias, stored, N, C, H, W, b8,
+                       ws, ws_bytes, stream);
 }
 
 SLR_EXPORT size_t slr_conv1x1_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int splits) {

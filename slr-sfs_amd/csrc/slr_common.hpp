@@ -15,12 +15,15 @@ namespace slr {
 // ---- error plumbing -------------------------------------------------------------------
 void set_error(const char *fmt, ...);
 
-#define SLR_CHECK_ARG(cond, what)                                              \
-    do { if (!(cond)) { slr::set_error("%s: bad argument: %s", __func__, what); return SLR_E_BADARG; } } while (0)
+// The *_FN forms name the entry point `fn` (a launcher shared by several exports reports the one that was called).
+#define SLR_CHECK_ARG_FN(fn, cond, what)                                       \
+    do { if (!(cond)) { slr::set_error("%s: bad argument: %s", fn, what); return SLR_E_BADARG; } } while (0)
+#define SLR_CHECK_ARG(cond, what) SLR_CHECK_ARG_FN(__func__, cond, what)
 
-#define SLR_CHECK_HIP(expr)                                                    \
+#define SLR_CHECK_HIP_FN(fn, expr)                                             \
     do { hipError_t e_ = (expr);                                               \
-         if (e_ != hipSuccess) { slr::set_error("%s: %s", __func__, hipGetErrorString(e_)); return (int)e_; } } while (0)
+         if (e_ != hipSuccess) { slr::set_error("%s: %s", fn, hipGetErrorString(e_)); return (int)e_; } } while (0)
+#define SLR_CHECK_HIP(expr) SLR_CHECK_HIP_FN(__func__, expr)
 
 #define SLR_CHECK_LAUNCH() SLR_CHECK_HIP(hipGetLastError())
 

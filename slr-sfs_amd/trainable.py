@@ -12,8 +12,9 @@ Then the rest of ResNet_Block_Pconv2 in training mode (blocks.py:173-248, DESIGN
 (partial) batch-norm with batch statistics + ReLU + mask (``bn_relu_mask_train``, ``TrainableNoiseBN``), the 1x1 skip convolution
 (``conv1x1``), differentiable ``avgpool_down`` / ``upsample_up``, and the block itself (``TrainablePconvResBlock``).
 
-Then the generator's networks (csrc/decoder_grad.hip): the decoder's first block, whose mask is (x != 0) per element
-(architectures.py:369) -- ``bn_relu_nonzero_train``, ``partial_conv_factors_counts``, ``partial_conv3x3_counts``,
+Then the generator's networks (the batch-norm's nonzero mask kind in csrc/block_grad.hip, csrc/decoder_grad.hip): the
+decoder's first block, whose mask is (x != 0) per element (architectures.py:369) -- ``bn_relu_nonzero_train``,
+``partial_conv_factors_counts``, ``partial_conv3x3_counts``,
 ``TrainablePconvInputBlock`` -- the plain ``TrainableResBlock`` (ResNet_Block, blocks.py:47-87) and the nets made of the two:
 ``TrainableDecoderPconv2``, ``TrainableEncoderWithZ``, ``TrainableEncoder``, ``TrainableBGDecoder``.
 
@@ -34,9 +35,8 @@ from ._lib import call, lib, require_device
 GRAD_X_B8, GRAD_G_B8 = 1, 2              # include/slr_splat.h: SLR_GRAD_X_B8 / SLR_GRAD_G_B8
 
 
-def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False, k=3, residual=None):
-    """Types, device, dtype, shapes and layouts -- before anything touches the device."""
-    tensors = (x, weight, bias, mask, residual)
+def _check_tensors(name, tensors):
+    """What every operator checks first of its tensors (None: an absent optional one): types, device, dtype, in this order."""
     for t in tensors:
         if t is not None and not torch.is_tensor(t):
             raise TypeError(f"slr_sfs_amd.{name}: tensors required, got {type(t).__name__}")
@@ -46,6 +46,20 @@ def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False, k=3, res
     for t in tensors:
         if t is not None and t.dtype != torch.float32:
             raise TypeError(f"slr_sfs_amd: float32 tensors required, got {t.dtype}")
+
+
+def _check_contiguous(name, tensors, labels=None):
+    """... and last, after their shapes: contiguity and one device."""
+    for i, t in enumerate(tensors):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name}: {labels[i] if labels else 'a tensor'} is not contiguous")
+    require_device(*tensors)
+
+
+def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False, k=3, residual=None):
+    """Types, device, dtype, shapes and layouts -- before anything touches the device."""
+    tensors = (x, weight, bias, mask, residual)
+    _check_tensors(name, tensors)
     if x.dim() != 4 or min(x.shape) < 1:
         raise ValueError(f"{name}: input [N,Cin,H,W] with N, Cin, H, W >= 1 required, got {tuple(x.shape)}")
     N, cin, H, W = x.shape
@@ -62,10 +76,7 @@ def _check(name, x, weight, bias, mask=None, in_b8=False, out_b8=False, k=3, res
         raise ValueError(f"{name}: a channel-blocked output needs Cout % 8 == 0, got {cout}")
     if residual is not None and tuple(residual.shape) != (N, cout, H, W):
         raise ValueError(f"{name}: residual {tuple(residual.shape)}, expected {(N, cout, H, W)}")
-    for label, t in (("input", x), ("weight", weight), ("bias", bias), ("mask", mask), ("residual", residual)):
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name}: {label} is not contiguous")
-    require_device(*tensors)
+    _check_contiguous(name, tensors, ("input", "weight", "bias", "mask", "residual"))
 
 
 class _Prepared(nets.Conv):
@@ -125,24 +136,33 @@ def _weights_of(weight, owner, sn, backward=False):
     return sn.buffer(weight, backward), nets.CONV_F32
 
 
-def _conv(x, buf, arith, bias, cout, layout, residual=None):
+def _conv(x, buf, arith, bias, cout, layout, residual=None, k=3):
+    """The k x k forward kernel (k = 3 or 1; the 1x1 entry point has no residual)."""
     N, cin, H, W = x.shape
     out = x.new_empty(N, cout, H, W)
-    call("slr_conv3x3_forward", x.device, x, buf, bias, residual, out, N, cin, cout, H, W, 1.0, 1.0, None, None, layout | arith)
+    if k == 1:
+        call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, 1.0, 1.0, layout | arith)
+    else:
+        call("slr_conv3x3_forward", x.device, x, buf, bias, residual, out, N, cin, cout, H, W, 1.0, 1.0, None, None, layout | arith)
     return out
 
 
-def _grad_ws(x, cout, splits=0):
-    N, cin, H, W = x.shape
-    nbytes = int(lib().slr_conv3x3_grad_ws_bytes(N, cin, cout, H, W, splits))
-    return torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+def _conv_backward_data(g, weight, owner, sn, in_b8, out_b8, k=3):
+    """The gradient to a convolution's input: the forward kernel with the flipped, transposed weight, the layouts swapped."""
+    buf, arith = _weights_of(weight, owner, sn, True)
+    return _conv(g, buf, arith, None, weight.shape[1], (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0), k=k)
 
 
-def _weight_grad(x, g, cout, want_bias, layout, splits=0):
+def _weight_grad(x, g, cout, want_bias, layout, splits=0, k=3):
+    """(dW, db or None).  The 3x3 entry point sums the bias gradient itself; the 1x1 one has no such output: ``_scale_bias`` does it."""
     N, cin, H, W = x.shape
-    dw = x.new_empty(cout, cin, 3, 3)
+    dw = x.new_empty(cout, cin, k, k)
+    ws_bytes = lib().slr_conv1x1_grad_ws_bytes if k == 1 else lib().slr_conv3x3_grad_ws_bytes
+    ws = torch.empty(int(ws_bytes(N, cin, cout, H, W, splits)), dtype=torch.uint8, device=x.device)
+    if k == 1:
+        call("slr_conv1x1_weight_grad", x.device, x, g, dw, N, cin, cout, H, W, splits, layout, ws, ws.numel())
+        return dw, (_scale_bias(g, None, None, False, True, layout & GRAD_G_B8)[1] if want_bias else None)
     db = x.new_empty(cout) if want_bias else None
-    ws = _grad_ws(x, cout, splits)
     call("slr_conv3x3_weight_grad", x.device, x, g, dw, db, N, cin, cout, H, W, splits, layout, ws, ws.numel())
     return dw, db
 
@@ -158,12 +178,17 @@ def _scale_bias(g, r, um, want_gr, want_bias, layout=0):
     return gr, db
 
 
-class _Conv3x3(torch.autograd.Function):
+class _Conv(torch.autograd.Function):
+    """The plain convolution, 3x3 or 1x1 by the weight's shape."""
+
     @staticmethod
     def forward(ctx, x, weight, bias, in_b8, out_b8, owner, residual=None, sn=None):
+        k = weight.shape[2]
+        if k == 1 and residual is not None:
+            raise ValueError("conv1x1: no residual (slr_conv1x1_forward has no such argument)")
         buf, arith = _weights_of(weight, owner, sn)
         layout = (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0) | (nets.RES_B8 if out_b8 and residual is not None else 0)
-        out = _conv(x, buf, arith, bias, weight.shape[0], layout, residual)
+        out = _conv(x, buf, arith, bias, weight.shape[0], layout, residual, k)
         ctx.save_for_backward(x, weight)
         ctx.cfg = (in_b8, out_b8, owner, bias is not None)
         ctx.sn = sn
@@ -175,15 +200,14 @@ class _Conv3x3(torch.autograd.Function):
         in_b8, out_b8, owner, has_bias = ctx.cfg
         g = g.contiguous()
         require_device(g)
-        cout, cin = weight.shape[:2]
+        cout, k = weight.shape[0], weight.shape[2]
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
         gx = gw = gb = None
         if need_x:
-            buf, arith = _weights_of(weight, owner, ctx.sn, True)
-            gx = _conv(g, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
+            gx = _conv_backward_data(g, weight, owner, ctx.sn, in_b8, out_b8, k)
         glayout = GRAD_G_B8 if out_b8 else 0
         if need_w:
-            gw, gb = _weight_grad(x, g, cout, need_b, (GRAD_X_B8 if in_b8 else 0) | glayout)
+            gw, gb = _weight_grad(x, g, cout, need_b, (GRAD_X_B8 if in_b8 else 0) | glayout, k=k)
             if ctx.sn is not None:
                 gw = ctx.sn.weight_grad(gw, weight)
         elif need_b:
@@ -204,7 +228,7 @@ def conv3x3(x, weight, bias=None, *, in_b8=False, out_b8=False, residual=None, w
     ``spectral_weight_grad``'s, (dW - <dW, W_eff> u v^T) / sigma.  Both None: exactly the operator without them."""
     _check("conv3x3", x, weight, bias, in_b8=in_b8, out_b8=out_b8, residual=residual)
     sn = _normalised("conv3x3", weight, weight_scale, spectral, _sn)
-    return _Conv3x3.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, residual, sn)
+    return _Conv.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, residual, sn)
 
 
 def partial_conv_factors(mask, cin):
@@ -215,6 +239,26 @@ def partial_conv_factors(mask, cin):
     um = torch.clamp(box, 0, 1)
     ratio = float(cin * 9) / (box + 1e-8) * um
     return ratio * um, um
+
+
+def _partial_conv_backward(ctx, g, xm, r, um, weight):
+    """The backward of both partial convolutions, whose inputs are (xm, mask or msum, weight, bias, owner, residual, ...): the gradient at
+    the raw convolution gr = g * r and the bias gradient sum g * um (``_scale_bias``), then backward-data and weight gradient of gr."""
+    owner, (in_b8, out_b8) = ctx.owner, ctx.layouts
+    g = g.contiguous()
+    require_device(g)
+    need_x, _, need_w, need_b = ctx.needs_input_grad[:4]
+    gx = gw = gb = None
+    glayout = GRAD_G_B8 if out_b8 else 0
+    if need_x or need_w or need_b:
+        gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
+        if need_x:
+            gx = _conv_backward_data(gr, weight, owner, ctx.sn, in_b8, out_b8)
+        if need_w:
+            gw, _ = _weight_grad(xm, gr, weight.shape[0], False, (GRAD_X_B8 if in_b8 else 0) | glayout)
+            if ctx.sn is not None:
+                gw = ctx.sn.weight_grad(gw, weight)
+    return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None, None    # (out = ... + residual)
 
 
 class _PartialConv3x3(torch.autograd.Function):
@@ -236,24 +280,8 @@ class _PartialConv3x3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_um):
         xm, mask, weight = ctx.saved_tensors
-        owner, (in_b8, out_b8) = ctx.owner, ctx.layouts
-        g = g.contiguous()
-        require_device(g)
-        cout, cin = weight.shape[:2]
-        need_x, _, need_w, need_b = ctx.needs_input_grad[:4]
-        gx = gw = gb = None
-        glayout = GRAD_G_B8 if out_b8 else 0
-        if need_x or need_w or need_b:
-            r, um = partial_conv_factors(mask, cin)
-            gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
-            if need_x:
-                buf, arith = _weights_of(weight, owner, ctx.sn, True)
-                gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
-            if need_w:
-                gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
-                if ctx.sn is not None:
-                    gw = ctx.sn.weight_grad(gw, weight)
-        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None, None    # (out = ... + residual)
+        r, um = partial_conv_factors(mask, weight.shape[1]) if any(ctx.needs_input_grad[:4]) else (None, None)
+        return _partial_conv_backward(ctx, g, xm, r, um, weight)
 
 
 def partial_conv3x3(xm, mask, weight, bias, *, residual=None, in_b8=False, out_b8=False, weight_scale=None, spectral=None, _owner=None,
@@ -285,6 +313,11 @@ def _w(conv):
     return conv.weight_orig if conv.spectral else conv.weight
 
 
+def _taken(conv):
+    """(weight, normalisation) of this forward: ``weight_orig`` with what the layer's ``SpectralGroup`` took for it, or (weight, None)."""
+    return _spectral.taken(conv) if conv.spectral else (conv.weight, None)
+
+
 class TrainableConv3x3(nets.Conv):
     """``nets.Conv(cin, cout, 3)`` whose parameters learn: same state-dict keys (``weight``, ``bias``), so what
     ``nets.load_reference_state_dict`` reads for a ``nets.Conv`` drops in."""
@@ -294,10 +327,8 @@ class TrainableConv3x3(nets.Conv):
         _learn(self, spectral)
 
     def forward(self, x, in_b8=False, out_b8=False, residual=None):
-        if self.spectral:
-            w, sn = _spectral.taken(self)
-            return conv3x3(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self, _sn=sn)
-        return conv3x3(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self)
+        w, sn = _taken(self)
+        return conv3x3(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, residual=residual, _owner=self, _sn=sn)
 
 
 class TrainablePartialConv3x3(nets.PartialConv):
@@ -308,10 +339,8 @@ class TrainablePartialConv3x3(nets.PartialConv):
         _learn(self, spectral)
 
     def forward(self, xm, mask, residual=None, in_b8=False, out_b8=False):
-        if self.spectral:
-            w, sn = _spectral.taken(self)
-            return partial_conv3x3(xm, mask, w, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
-        return partial_conv3x3(xm, mask, self.weight, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self)
+        w, sn = _taken(self)
+        return partial_conv3x3(xm, mask, w, self.bias, residual=residual, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
 
 
 # --------------------------------------------------------------------------- the rest of the block (csrc/block_grad.hip)
@@ -319,15 +348,7 @@ class TrainablePartialConv3x3(nets.PartialConv):
 def _check_planes(name, x, b8, mask=None, tables=(), like=()):
     """The same checks for the operators on [N,C,H,W] planes: ``tables`` are [N,C], ``like`` tensors of x's shape."""
     tensors = (x, mask, *tables, *like)
-    for t in tensors:
-        if t is not None and not torch.is_tensor(t):
-            raise TypeError(f"slr_sfs_amd.{name}: tensors required, got {type(t).__name__}")
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise NotImplementedError("slr_sfs_amd operators run on ROCm device tensors only (no CPU path)")
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"slr_sfs_amd: float32 tensors required, got {t.dtype}")
+    _check_tensors(name, tensors)
     if x.dim() != 4 or min(x.shape) < 1:
         raise ValueError(f"{name}: input [N,C,H,W] with N, C, H, W >= 1 required, got {tuple(x.shape)}")
     N, C, H, W = x.shape
@@ -343,49 +364,57 @@ def _check_planes(name, x, b8, mask=None, tables=(), like=()):
         raise ValueError(f"{name}: a channel-blocked tensor needs C % 8 == 0, got {C}")
     if N * C > 65535:
         raise ValueError(f"{name}: N * C <= 65535 required, got {N * C}")
-    for t in tensors:
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name}: a tensor is not contiguous")
-    require_device(*tensors)
+    _check_contiguous(name, tensors)
 
 
-def _bn_ws(x):
-    return torch.empty(int(lib().slr_bn_train_ws_bytes(*x.shape)), dtype=torch.uint8, device=x.device)
+# entry points of the two mask kinds (csrc/block_grad.hip): workspace size, statistics, forward, backward
+_BN_PLANE = ("slr_bn_train_ws_bytes", "slr_bn_batch_stats", "slr_bn_relu_mask_train", "slr_bn_relu_mask_backward")
+_BN_NONZERO = ("slr_bn_nonzero_ws_bytes", "slr_bn_nonzero_stats", "slr_bn_relu_nonzero_train", "slr_bn_relu_nonzero_backward")
 
 
-class _BnReluMaskTrain(torch.autograd.Function):
-    """(a, mean, var[, x]) -- with ``fork`` the input comes back as a second output whose gradient the backward adds to dx in its
-    elementwise pass (the block input feeds bn1 and the skip branch)."""
+class _BnReluTrain(torch.autograd.Function):
+    """(a, mean, var[, msum][, x]).  ``nonzero``: the mask is k = [x != 0], recomputed from x by every kernel (``mask`` is None then); the
+    statistics' count is one per channel, and msum = sum_c k comes back for the partial convolution behind.  With ``fork`` the input comes
+    back as the last output, whose gradient the backward adds to dx in its elementwise pass (the block input feeds bn1 and the skip
+    branch)."""
 
     @staticmethod
-    def forward(ctx, x, mask, gain, bias, mean, var, eps, b8, fork):
+    def forward(ctx, x, mask, gain, bias, mean, var, eps, b8, fork, nonzero):
         N, C, H, W = x.shape
+        ws_bytes, stats, train, _ = _BN_NONZERO if nonzero else _BN_PLANE
+        m = () if nonzero else (mask,)                   # (the plane entry points take the mask, in the places below)
         stored = mean is not None
         count = None
         if not stored:
-            mean, var, count = x.new_empty(C), x.new_empty(C), x.new_empty(1)
-            ws = _bn_ws(x)
-            call("slr_bn_batch_stats", x.device, x, mask, eps, mean, var, count, N, C, H, W, int(b8), ws, ws.numel())
+            mean, var, count = x.new_empty(C), x.new_empty(C), x.new_empty(C if nonzero else 1)
+            ws = torch.empty(int(getattr(lib(), ws_bytes)(N, C, H, W)), dtype=torch.uint8, device=x.device)
+            call(stats, x.device, x, *m, eps, mean, var, count, N, C, H, W, int(b8), ws, ws.numel())
         scale, shift = x.new_empty(N, C), x.new_empty(N, C)
         call("slr_bn_train_tables", x.device, mean, var, gain, bias, eps, scale, shift, N, C)
         a = torch.empty_like(x)
-        call("slr_bn_relu_mask_train", x.device, x, scale, shift, mask, a, N, C, H, W, int(b8))
+        call(train, x.device, x, scale, shift, *m, a, N, C, H, W, int(b8))
         ctx.save_for_backward(x, mask, gain, scale, shift, mean, var, count)
-        ctx.cfg = (eps, b8, stored, bias is not None)
+        ctx.cfg = (eps, b8, stored, bias is not None, fork, nonzero)
         ctx.set_materialize_grads(False)
-        if stored:
-            return (a, None, None, x) if fork else (a, None, None)
-        ctx.mark_non_differentiable(mean, var)
-        return (a, mean, var, x) if fork else (a, mean, var)
+        out = (a, None, None) if stored else (a, mean, var)
+        if nonzero:
+            msum = x.new_empty(N, 1, H, W)
+            call("slr_nonzero_count_plane", x.device, x, msum, N, C, H, W, int(b8))
+            out += (msum,)
+        ctx.mark_non_differentiable(*(t for t in out[1:] if t is not None))       # (one call: a second one replaces the first)
+        return out + (x,) if fork else out
 
     @staticmethod
-    def backward(ctx, ga, _gm=None, _gv=None, gskip=None):
+    def backward(ctx, ga, *grads):
         x, mask, gain, scale, shift, mean, var, count = ctx.saved_tensors
-        eps, b8, stored, has_bias = ctx.cfg
+        eps, b8, stored, has_bias, fork, nonzero = ctx.cfg
+        ws_bytes, _, _, backward = _BN_NONZERO if nonzero else _BN_PLANE
+        gskip = grads[-1] if fork else None              # (the gradients of mean, var and msum are not used)
         N, C, H, W = x.shape
         need_x, need_g, need_b = ctx.needs_input_grad[0], gain is not None and ctx.needs_input_grad[2], has_bias and ctx.needs_input_grad[3]
+        none = (None,) * 9
         if ga is None:                                   # only the skip branch was used
-            return (gskip if need_x else None), None, None, None, None, None, None, None, None
+            return ((gskip if need_x else None),) + none
         ga = ga.contiguous()
         require_device(ga)
         addend = None
@@ -396,11 +425,29 @@ class _BnReluMaskTrain(torch.autograd.Function):
         dgain = x.new_empty(N, C) if need_g else None
         dbias = x.new_empty(N, C) if need_b else None
         if dx is None and dgain is None and dbias is None:
-            return (None,) * 9
-        ws = _bn_ws(x) if (not stored or need_g or need_b) else None
-        call("slr_bn_relu_mask_backward", x.device, x, ga, mask, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias,
+            return (None,) + none
+        ws = None
+        if not stored or need_g or need_b:
+            ws = torch.empty(int(getattr(lib(), ws_bytes)(N, C, H, W)), dtype=torch.uint8, device=x.device)
+        call(backward, x.device, x, ga, *(() if nonzero else (mask,)), scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias,
              int(stored), N, C, H, W, int(b8), ws, 0 if ws is None else ws.numel())
-        return dx, None, dgain, dbias, None, None, None, None, None
+        return (dx, None, dgain, dbias) + none[:6]
+
+
+def _bn_relu_train(name, x, mask, gain, bias, mean, var, eps, b8, fork, nonzero):
+    """The checks and the call both mask kinds share; with stored statistics the caller's own mean and var come back."""
+    _check_planes(name, x, b8, mask, (gain, bias))
+    if (mean is None) != (var is None):
+        raise ValueError(f"{name}: mean and var go together")
+    if mean is not None:
+        for t in (mean, var):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
+                raise ValueError(f"{name}: mean / var: contiguous float32 device tensors ({x.shape[1]},) required")
+        mean, var = mean.detach(), var.detach()
+    out = _BnReluTrain.apply(x, None if mask is None else mask.detach(), gain, bias, mean, var, float(eps), bool(b8), bool(fork), nonzero)
+    if mean is not None:
+        out = (out[0], mean, var) + tuple(out[3:])
+    return out
 
 
 def bn_relu_mask_train(x, mask, gain, bias, *, mean=None, var=None, eps=1e-5, b8=False, fork=False):
@@ -413,60 +460,7 @@ def bn_relu_mask_train(x, mask, gain, bias, *, mean=None, var=None, eps=1e-5, b8
     fork=True returns (a, mean, var, x): x again as an output of the same node, for a second consumer of x (the block's skip branch).  The
     gradient arriving at that output is added to dx inside the backward's elementwise pass (the entry point's ``addend``) instead of
     in a pass of its own by autograd."""
-    _check_planes("bn_relu_mask_train", x, b8, mask, (gain, bias))
-    if (mean is None) != (var is None):
-        raise ValueError("bn_relu_mask_train: mean and var go together")
-    if mean is not None:
-        for t in (mean, var):
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
-                raise ValueError(f"bn_relu_mask_train: mean / var: contiguous float32 device tensors ({x.shape[1]},) required")
-        mean, var = mean.detach(), var.detach()
-    out = _BnReluMaskTrain.apply(x, None if mask is None else mask.detach(), gain, bias, mean, var, float(eps), bool(b8), bool(fork))
-    if mean is not None:
-        out = (out[0], mean, var) + tuple(out[3:])
-    return out
-
-
-class _Conv1x1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, in_b8, out_b8, owner, sn=None):
-        buf, arith = _weights_of(weight, owner, sn)
-        out = _conv1(x, buf, arith, bias, weight.shape[0], (nets.IN_B8 if in_b8 else 0) | (nets.OUT_B8 if out_b8 else 0))
-        ctx.save_for_backward(x, weight)
-        ctx.cfg = (in_b8, out_b8, owner, bias is not None)
-        ctx.sn = sn
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, weight = ctx.saved_tensors
-        in_b8, out_b8, owner, has_bias = ctx.cfg
-        g = g.contiguous()
-        require_device(g)
-        N, cin, H, W = x.shape
-        cout = weight.shape[0]
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        gx = gw = gb = None
-        if need_x:                                       # the forward kernel with the transposed weight
-            buf, arith = _weights_of(weight, owner, ctx.sn, True)
-            gx = _conv1(g, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
-        glayout = GRAD_G_B8 if out_b8 else 0
-        if need_w:
-            gw = x.new_empty(cout, cin, 1, 1)
-            ws = torch.empty(int(lib().slr_conv1x1_grad_ws_bytes(N, cin, cout, H, W, 0)), dtype=torch.uint8, device=x.device)
-            call("slr_conv1x1_weight_grad", x.device, x, g, gw, N, cin, cout, H, W, 0, (GRAD_X_B8 if in_b8 else 0) | glayout, ws, ws.numel())
-            if ctx.sn is not None:
-                gw = ctx.sn.weight_grad(gw, weight)
-        if need_b:
-            _, gb = _scale_bias(g, None, None, False, True, glayout)
-        return gx, gw, gb, None, None, None, None
-
-
-def _conv1(x, buf, arith, bias, cout, layout):
-    N, cin, H, W = x.shape
-    out = x.new_empty(N, cout, H, W)
-    call("slr_conv1x1_forward", x.device, x, buf, bias, out, N, cin, cout, H, W, 1.0, 1.0, layout | arith)
-    return out
+    return _bn_relu_train("bn_relu_mask_train", x, mask, gain, bias, mean, var, eps, b8, fork, False)
 
 
 def conv1x1(x, weight, bias=None, *, in_b8=False, out_b8=False, weight_scale=None, spectral=None, _owner=None, _sn=None):
@@ -474,7 +468,7 @@ def conv1x1(x, weight, bias=None, *, in_b8=False, out_b8=False, weight_scale=Non
     differentiable in x, weight and bias; in_b8 / out_b8, weight_scale / spectral as ``conv3x3``."""
     _check("conv1x1", x, weight, bias, in_b8=in_b8, out_b8=out_b8, k=1)
     sn = _normalised("conv1x1", weight, weight_scale, spectral, _sn)
-    return _Conv1x1.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, sn)
+    return _Conv.apply(x, weight, bias, bool(in_b8), bool(out_b8), _owner, None, sn)
 
 
 class _Resample(torch.autograd.Function):
@@ -516,10 +510,8 @@ class TrainableConv1x1(nets.Conv):
         _learn(self, spectral)
 
     def forward(self, x, in_b8=False, out_b8=False):
-        if self.spectral:
-            w, sn = _spectral.taken(self)
-            return conv1x1(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
-        return conv1x1(x, self.weight, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self)
+        w, sn = _taken(self)
+        return conv1x1(x, w, self.bias, in_b8=in_b8, out_b8=out_b8, _owner=self, _sn=sn)
 
 
 class TrainableNoiseBN(nn.Module):
@@ -559,6 +551,29 @@ class TrainableNoiseBN(nn.Module):
         return out
 
 
+def _block_forward(block, b8_in, noise, first):
+    """What the three blocks' forwards share -> (y, update mask or None, b8_out).  ``first(noise1, b8)`` -> (a, mask or None, x again): the
+    block's own bn1 + conv_aa, bn1 called with fork=True.  Then bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue -> one resampling of the
+    sum (both resamplers are linear, as in ``nets.PconvResBlock``).  A mask selects the partial form of bn2 and conv_ab."""
+    if block.spectral:
+        _spectral.begin(block)
+    cout = _w(block.conv_aa).shape[0]
+    b8 = cout % 8 == 0 if block.conv_b is not None else bool(b8_in)
+    n1, n2 = noise if noise is not None else (None, None)
+    a, m, xs = first(n1, b8)
+    a = block.bn2(a, m, n2, b8=b8)[0]                                                # blocks.py:233-238 / 73-75
+    skip = block.conv_b(xs, in_b8=b8_in, out_b8=b8) if block.conv_b is not None else xs      # :243-247 / 78-81
+    if m is None:
+        a = block.conv_ab(a, in_b8=b8, out_b8=b8, residual=skip)                     # :87
+    else:
+        a, m = block.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)               # :239, 248
+    if block.kind == "Up":
+        a = upsample_up(a, b8)
+    elif block.kind:
+        a = avgpool_down(a, b8)
+    return a, m, b8
+
+
 class TrainablePconvResBlock(nets.PconvResBlock):
     """``nets.PconvResBlock`` (ResNet_Block_Pconv2 with pconv_pbn_woresbias, blocks.py:173-248) as one differentiable unit in training or
     eval mode: same sub-module names and state-dict keys (``nets.load_reference_state_dict`` fills it), the BNs with their noise weights
@@ -581,79 +596,15 @@ class TrainablePconvResBlock(nets.PconvResBlock):
         if mask is None:
             raise ValueError("TrainablePconvResBlock: an explicit mask [N,1,H,W] is required (the per-element mask x != 0 is TrainablePconvInputBlock's)")
         _check_planes("TrainablePconvResBlock", x, b8_in, mask)
-        if self.spectral:
-            _spectral.begin(self)
-        cout = _w(self.conv_aa).shape[0]
-        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
-        n1, n2 = noise if noise is not None else (None, None)
-        a, _, _, xs = self.bn1(x, mask, n1, b8=b8_in, fork=True)                    # blocks.py:225-231
-        a, m = self.conv_aa(a, mask, in_b8=b8_in, out_b8=b8)
-        a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238
-        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs        # :243-247
-        a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)                # :239, 248
-        if self.kind == "Up":
-            a = upsample_up(a, b8)
-        elif self.kind:
-            a = avgpool_down(a, b8)
+
+        def first(n1, b8):                               # blocks.py:225-231
+            a, _, _, xs = self.bn1(x, mask, n1, b8=b8_in, fork=True)
+            return self.conv_aa(a, mask, in_b8=b8_in, out_b8=b8) + (xs,)
+        a, m, b8 = _block_forward(self, b8_in, noise, first)
         return a, self.resample_mask(m), b8
 
 
 # --------------------------------------------------------------------------- the decoder's first block (csrc/decoder_grad.hip)
-
-def _nz_ws(x):
-    return torch.empty(int(lib().slr_bn_nonzero_ws_bytes(*x.shape)), dtype=torch.uint8, device=x.device)
-
-
-class _BnReluNonzeroTrain(torch.autograd.Function):
-    """(a, mean, var, msum[, x]): ``_BnReluMaskTrain`` with the mask k = [x != 0] recomputed from x by every kernel."""
-
-    @staticmethod
-    def forward(ctx, x, gain, bias, mean, var, eps, b8, fork):
-        N, C, H, W = x.shape
-        stored = mean is not None
-        count = None
-        if not stored:
-            mean, var, count = x.new_empty(C), x.new_empty(C), x.new_empty(C)
-            ws = _nz_ws(x)
-            call("slr_bn_nonzero_stats", x.device, x, eps, mean, var, count, N, C, H, W, int(b8), ws, ws.numel())
-        scale, shift = x.new_empty(N, C), x.new_empty(N, C)
-        call("slr_bn_train_tables", x.device, mean, var, gain, bias, eps, scale, shift, N, C)
-        a, msum = torch.empty_like(x), x.new_empty(N, 1, H, W)
-        call("slr_bn_relu_nonzero_train", x.device, x, scale, shift, a, N, C, H, W, int(b8))
-        call("slr_nonzero_count_plane", x.device, x, msum, N, C, H, W, int(b8))
-        ctx.save_for_backward(x, gain, scale, shift, mean, var, count)
-        ctx.cfg = (eps, b8, stored, bias is not None)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(msum)
-        if stored:
-            return (a, None, None, msum, x) if fork else (a, None, None, msum)
-        ctx.mark_non_differentiable(mean, var)
-        return (a, mean, var, msum, x) if fork else (a, mean, var, msum)
-
-    @staticmethod
-    def backward(ctx, ga, _gm=None, _gv=None, _gs=None, gskip=None):
-        x, gain, scale, shift, mean, var, count = ctx.saved_tensors
-        eps, b8, stored, has_bias = ctx.cfg
-        N, C, H, W = x.shape
-        need_x, need_g, need_b = ctx.needs_input_grad[0], gain is not None and ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        if ga is None:                                   # only the skip branch was used
-            return (gskip if need_x else None), None, None, None, None, None, None, None
-        ga = ga.contiguous()
-        require_device(ga)
-        addend = None
-        if need_x and gskip is not None:
-            addend = gskip.contiguous()
-            require_device(addend)
-        dx = torch.empty_like(x) if need_x else None
-        dgain = x.new_empty(N, C) if need_g else None
-        dbias = x.new_empty(N, C) if need_b else None
-        if dx is None and dgain is None and dbias is None:
-            return (None,) * 8
-        ws = _nz_ws(x) if (not stored or need_g or need_b) else None
-        call("slr_bn_relu_nonzero_backward", x.device, x, ga, scale, shift, mean, var, gain, count, eps, addend, dx, dgain, dbias,
-             int(stored), N, C, H, W, int(b8), ws, 0 if ws is None else ws.numel())
-        return dx, dgain, dbias, None, None, None, None, None
-
 
 def bn_relu_nonzero_train(x, gain, bias, *, mean=None, var=None, eps=1e-5, b8=False, fork=False):
     """``bn_relu_mask_train`` with the per-element mask k = (x != 0) of the decoder's first block (architectures.py:369; the mask is never
@@ -661,18 +612,7 @@ def bn_relu_nonzero_train(x, gain, bias, *, mean=None, var=None, eps=1e-5, b8=Fa
     [N,C,H,W] mask), a = relu(x * scale - shift) * k.  Returns (a, mean, var, msum[, x]) with msum [N,1,H,W] = sum_c k, what the partial
     convolution behind it needs (``partial_conv3x3_counts``).  Differentiable in x, gain and bias; the gradient through the statistics
     reaches the zero elements of x too, as the reference's autograd gives it.  mean / var, b8 and fork as ``bn_relu_mask_train``."""
-    _check_planes("bn_relu_nonzero_train", x, b8, None, (gain, bias))
-    if (mean is None) != (var is None):
-        raise ValueError("bn_relu_nonzero_train: mean and var go together")
-    if mean is not None:
-        for t in (mean, var):
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
-                raise ValueError(f"bn_relu_nonzero_train: mean / var: contiguous float32 device tensors ({x.shape[1]},) required")
-        mean, var = mean.detach(), var.detach()
-    out = _BnReluNonzeroTrain.apply(x, gain, bias, mean, var, float(eps), bool(b8), bool(fork))
-    if mean is not None:
-        out = (out[0], mean, var) + tuple(out[3:])
-    return out
+    return _bn_relu_train("bn_relu_nonzero_train", x, None, gain, bias, mean, var, eps, b8, fork, True)
 
 
 def _factors_counts(msum, cin):
@@ -709,24 +649,7 @@ class _PartialConv3x3Counts(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g_um):
-        xm, r, um, weight = ctx.saved_tensors
-        owner, (in_b8, out_b8) = ctx.owner, ctx.layouts
-        g = g.contiguous()
-        require_device(g)
-        cout, cin = weight.shape[:2]
-        need_x, _, need_w, need_b = ctx.needs_input_grad[:4]
-        gx = gw = gb = None
-        glayout = GRAD_G_B8 if out_b8 else 0
-        if need_x or need_w or need_b:                   # from here on exactly _PartialConv3x3.backward
-            gr, gb = _scale_bias(g, r, um, need_x or need_w, need_b, glayout)
-            if need_x:
-                buf, arith = _weights_of(weight, owner, ctx.sn, True)
-                gx = _conv(gr, buf, arith, None, cin, (nets.IN_B8 if out_b8 else 0) | (nets.OUT_B8 if in_b8 else 0))
-            if need_w:
-                gw, _ = _weight_grad(xm, gr, cout, False, (GRAD_X_B8 if in_b8 else 0) | glayout)
-                if ctx.sn is not None:
-                    gw = ctx.sn.weight_grad(gw, weight)
-        return gx, None, gw, gb, None, (g if ctx.needs_input_grad[5] else None), None, None, None
+        return _partial_conv_backward(ctx, g, *ctx.saved_tensors)
 
 
 def partial_conv3x3_counts(xm, msum, weight, bias, *, residual=None, in_b8=False, out_b8=False, weight_scale=None, spectral=None,
@@ -749,21 +672,12 @@ class TrainablePconvInputBlock(TrainablePconvResBlock):
     def forward(self, x, b8_in=False, noise=None):
         """-> (y, update_mask, b8_out); arguments as the parent's, without the mask."""
         _check_planes("TrainablePconvInputBlock", x, b8_in)
-        if self.spectral:
-            _spectral.begin(self)
-        cout = _w(self.conv_aa).shape[0]
-        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
-        n1, n2 = noise if noise is not None else (None, None)
-        a, _, _, msum, xs = self.bn1(x, None, n1, b8=b8_in, fork=True, nonzero=True)             # blocks.py:225-231
-        w, sn = _spectral.taken(self.conv_aa) if self.spectral else (self.conv_aa.weight, None)
-        a, m = partial_conv3x3_counts(a, msum, w, self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa, _sn=sn)
-        a = self.bn2(a, m, n2, b8=b8)[0]                                             # :233-238 -- the mask is channel-uniform from here
-        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs
-        a, m = self.conv_ab(a, m, residual=skip, in_b8=b8, out_b8=b8)
-        if self.kind == "Up":
-            a = upsample_up(a, b8)
-        elif self.kind:
-            a = avgpool_down(a, b8)
+
+        def first(n1, b8):                               # blocks.py:225-231 -- the mask is channel-uniform after conv_aa
+            a, _, _, msum, xs = self.bn1(x, None, n1, b8=b8_in, fork=True, nonzero=True)
+            w, sn = _taken(self.conv_aa)
+            return partial_conv3x3_counts(a, msum, w, self.conv_aa.bias, in_b8=b8_in, out_b8=b8, _owner=self.conv_aa, _sn=sn) + (xs,)
+        a, m, b8 = _block_forward(self, b8_in, noise, first)
         return a, self.resample_mask(m), b8
 
 
@@ -785,20 +699,11 @@ class TrainableResBlock(nets.ResBlock):
     def forward(self, x, b8_in=False, noise=None):
         """-> (y, b8_out).  bn1 -> conv_aa -> bn2 -> conv_ab + conv_b(x) (or + x) in its epilogue -> one resampling of the sum."""
         _check_planes("TrainableResBlock", x, b8_in)
-        if self.spectral:
-            _spectral.begin(self)
-        cout = _w(self.conv_aa).shape[0]
-        b8 = cout % 8 == 0 if self.conv_b is not None else bool(b8_in)
-        n1, n2 = noise if noise is not None else (None, None)
-        a, _, _, xs = self.bn1(x, None, n1, b8=b8_in, fork=True)                    # blocks.py:69-72
-        a = self.conv_aa(a, in_b8=b8_in, out_b8=b8)
-        a = self.bn2(a, None, n2, b8=b8)[0]                                          # :73-75
-        skip = self.conv_b(xs, in_b8=b8_in, out_b8=b8) if self.conv_b is not None else xs        # :78-81
-        a = self.conv_ab(a, in_b8=b8, out_b8=b8, residual=skip)                      # :87
-        if self.kind == "Up":
-            a = upsample_up(a, b8)
-        elif self.kind:
-            a = avgpool_down(a, b8)
+
+        def first(n1, b8):                               # blocks.py:69-72
+            a, _, _, xs = self.bn1(x, None, n1, b8=b8_in, fork=True)
+            return self.conv_aa(a, in_b8=b8_in, out_b8=b8), None, xs
+        a, _, b8 = _block_forward(self, b8_in, noise, first)
         return a, b8
 
 

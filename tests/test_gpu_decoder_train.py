@@ -24,7 +24,9 @@ from metrics_fixture import from_blocked, to_blocked
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-BN_SHAPES = ((1, 8, 5, 7), (2, 24, 33, 20), (2, 64, 37, 51), (2, 130, 4, 4))
+# (2, 8, 3, 2751): H W = 8253, where the reductions with eight items per thread need more than one workgroup per plane (2 in NCHW, 5
+# channel-blocked), the plane ends in a one-pixel item and most threads of the last workgroup have no item -- over two images
+BN_SHAPES = ((1, 8, 5, 7), (2, 24, 33, 20), (2, 64, 37, 51), (2, 130, 4, 4), (2, 8, 3, 2751))
 PC_SHAPES = ((2, 16, 24, 13, 10), (2, 64, 64, 37, 51), (1, 8, 3, 5, 7))                # N, Cin, Cout, H, W
 IN_BLOCKS = ((2, 16, 24, 13, 10, None), (2, 24, 24, 12, 10, None), (2, 16, 40, 12, 12, "Down"), (2, 40, 16, 6, 5, "Up"), (2, 16, 3, 8, 8, None))
 RES_BLOCKS = ((2, 3, 16, 9, 10, None), (2, 16, 16, 8, 8, None), (2, 16, 24, 12, 12, "Down"), (2, 24, 16, 6, 5, "Up"), (2, 16, 9, 8, 8, None))
@@ -151,6 +153,7 @@ def _run_nz(S, c, b8, need=(True, True, True), addend=False):
     st = {} if c["st"] is None else dict(mean=c["st"][0].to(DEV), var=c["st"][1].to(DEV))
     with _no_sync():
         out = S.bn_relu_nonzero_train(x, gain, bias, b8=b8, fork=addend, **st)
+        assert not any(t.requires_grad for t in out[1:4])     # mean, var and msum carry no gradient, whatever the inputs do
         if addend:
             torch.autograd.backward([out[0], out[4]], [ga, add])
         else:

@@ -10,7 +10,7 @@ crop, two ways in one process with the same seeded weights and noise:
 Cases: the decoder at [2,64,256,256], EncoderWithZ at [2,3,256,256].  Per case: warm-up, then A and B alternated (ROUNDS rounds of STEPS
 steps, device events around every block of steps; the median with the min - max of the rounds), the peak memory of a step of each, and
 -- unless --no-trace -- one child process per variant under `rocprofv3 --kernel-trace` for the sum of kernel time, the launches per step
-and the time of every kernel of csrc/decoder_grad.hip, those of the decoder against the bytes they must move at block 0's shape and
+and the time of every kernel only the decoder's first block launches, those of the decoder against the bytes they must move at block 0's shape and
 8 TB/s.  No threshold: the numbers are recorded.  Prints one JSON document (--out FILE writes it too).  A device is required.
 
     python tools/decoder_train_bench.py --out profiles/decoder_train_step.json
@@ -32,12 +32,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CASES = {"decoder_2x64x256x256": ("decoder", 2, 64, 256, 256), "encoder_with_z_2x3x256x256": ("encoder", 2, 3, 256, 256)}
-NEW_KERNELS = ("nz_stats", "nz_count_plane", "nz_forward", "nz_backward", "pconv_train_epilogue")
 EPS = 1e-5
 HBM = 8e12
-# bytes the five tensor-sized kernels of csrc/decoder_grad.hip must move per element of the decoder's block 0 (64 -> 64, identity skip),
-# in tensors of 4 N C H W bytes: x | x (+ plane) | x, a | x, ga | x, ga, addend, dx | raw, residual, out
-TENSORS_MOVED = {"nz_stats_kernel": 1, "nz_count_plane": 1, "nz_forward": 2, "nz_backward_reduce": 2, "nz_backward_dx": 4, "pconv_train_epilogue": 3}
+# bytes the tensor-sized kernels of the decoder's first block must move per element of it (64 -> 64, identity skip), in tensors of
+# 4 N C H W bytes: x | x (+ plane) | x, a | x, ga | x, ga, addend, dx | raw, residual, out.  The batch-norm kernels are the nonzero-mask
+# instantiations `<layout, true...` of csrc/block_grad.hip's family, the other two csrc/decoder_grad.hip's.
+_NONZERO_BN = {"bn_stats_kernel": 1, "bn_train_forward_kernel": 2, "bn_backward_reduce_kernel": 2, "bn_backward_dx_kernel": 4}
+TENSORS_MOVED = {f"{k}<{b8}, true": t for k, t in _NONZERO_BN.items() for b8 in ("false", "true")}
+TENSORS_MOVED.update({"nz_count_plane": 1, "pconv_train_epilogue": 3})
+# (the two finalize kernels are shared with the batch-norms of all other blocks: their rows sum over every block of the net)
+NEW_KERNELS = tuple(TENSORS_MOVED) + ("bn_stats_final_kernel", "bn_backward_final_kernel")
 
 
 def make_case(case):
