@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SLR_ABI_VERSION 27
+#define SLR_ABI_VERSION 28
 
 #define SLR_E_BADARG   (-1)   /* null pointer / non-positive size / unknown enum  */
 #define SLR_E_WORKSPACE (-2)  /* workspace too small or misaligned                */
@@ -96,6 +96,28 @@ int slr_euler_integrate_batch(const float *motion, const long long *steps, int B
  *   grad_disp [B,2,H,W] in;  grad_motion [B,2,H,W] out (zeroed here) */
 int slr_euler_backward_batch(const float *motion, const long long *steps, int B, int H, int W, float sign,
                              const float *grad_disp, float *grad_motion, void *stream);
+
+/* ABI 28.  Both integrations of the training step (animating_softmax_splating.py:579-580) as one operator.
+ * Forward: ONE launch, the direction a grid dimension: disp_f = the integration of +motion for steps_f[b] steps, disp_p = that of
+ * -motion for steps_p[b] steps; per sample and direction the bits of slr_euler_integrate_batch with sign = +1 / -1.
+ *   motion [B,2,H,W];  steps_f, steps_p [B] int64 ON THE DEVICE;  disp_f, disp_p [B,2,H,W] out;  vis_f, vis_p [B,H,W] out, may be NULL. */
+int slr_euler_pair_forward(const float *motion, const long long *steps_f, const long long *steps_p, int B, int H, int W,
+                           float *disp_f, float *disp_p, float *vis_f, float *vis_p, void *stream);
+
+/* Gradient of both displacements w.r.t. `motion` as one tensor: slr_euler_backward_batch(+1, gdisp_f) + slr_euler_backward_batch(-1,
+ * gdisp_p) by definition, but summed in 64-bit fixed point with integer atomics, so grad_motion is the same bits whatever order the
+ * contributions arrive in (run to run, alone or inside a batch).  Three launches: scale (zeroes the workspace, largest finite |g| per
+ * sample), walk (one work-item per sample, direction and pixel; consecutive steps in one cell are one addition), finish (writes EVERY
+ * element of grad_motion).  Per cell with K visits and exact sum s:  |out - s| <= Q + 2^-24 (|s| + Q),  Q = K 2^(e-F-1), where
+ * 2^(e-1) <= largest finite |g| of the sample < 2^e and F = min(60, 63 - ceil(log2((steps_f[b] + steps_p[b]) H W))) (csrc/euler.hip has
+ * the derivation).  A non-finite g goes to the cells of its pixel's path and nowhere else, as a canonical NaN or an infinity.
+ *   workspace: slr_euler_pair_workspace_bytes(B, H, W) = B (1280 + 24 H W) bytes, 8-byte aligned, contents irrelevant on entry; on
+ *   return sample b's first four ints (byte offset 1280 b) hold {e, F, bits of the largest finite |g|, 0}.
+ * slr_euler_pair_workspace_bytes returns 0 for sizes the operator refuses (B outside 1..65535, H W >= 2^30). */
+size_t slr_euler_pair_workspace_bytes(int B, int H, int W);
+int slr_euler_pair_backward(const float *motion, const long long *steps_f, const long long *steps_p, int B, int H, int W,
+                            const float *gdisp_f, const float *gdisp_p, float *grad_motion, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 /* ------------------------------------------------------------------ splat: workspace, binning, front ends */
 

@@ -28,11 +28,11 @@ from . import motion_training  # noqa: F401
 from .motion_training import (conv4x4s2, instnorm_spade_train, upsample2x_concat_train, motion_losses, MotionLoss,  # noqa: F401
                               TrainableSPADEIN, TrainableSPADEUnet4MaskMotion, MotionTrainingModel)
 from . import model  # noqa: F401
-from .model import TrainingModel, Trainer  # noqa: F401
+from .model import TrainingModel, Trainer, JointTrainingModel, check_joint_options  # noqa: F401
 from . import layers  # noqa: F401
 from .layers import layer_composite, alpha_losses, blend_alpha0, TwoLayerTrainingModel, TwoLayerAlpha0TrainingModel  # noqa: F401
 from .softsplat import FunctionSoftsplat, ModuleSoftsplat, ModuleMaximumsplat, ModuleMaximumWarpNormsplat  # noqa: F401
-from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all  # noqa: F401
+from .euler_integration_manipulator import euler_integration, EulerIntegration, euler_integration_all, euler_integration_pair  # noqa: F401
 from .dropin import install_into_reference  # noqa: F401
 
 __version__ = "0.1.0"

@@ -7,7 +7,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLR_SFS_AMD_LIB") or os.path.join(_HERE, "lib", "libslrsplat.so")   # env: dev only
-ABI_VERSION = 27
+ABI_VERSION = 28
 WS_PREBINNED, WS_CLEAN = 1, 2       # include/slr_splat.h: flags of the `prebinned` argument
 BLEND_DETERMINISTIC = 1             # ... of slr_splat_blend_forward_ex's `flags`
 
@@ -22,6 +22,9 @@ SIGNATURES = {
     "slr_euler_backward": (_i, [_fp, _i, _i, _i, _f, _fp, _fp, _vp]),
     "slr_euler_integrate_batch": (_i, [_fp, _vp, _i, _i, _i, _f, _fp, _fp, _vp]),
     "slr_euler_backward_batch": (_i, [_fp, _vp, _i, _i, _i, _f, _fp, _fp, _vp]),
+    "slr_euler_pair_forward": (_i, [_fp, _vp, _vp, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
+    "slr_euler_pair_workspace_bytes": (_sz, [_i, _i, _i]),
+    "slr_euler_pair_backward": (_i, [_fp, _vp, _vp, _i, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
     "slr_splat_workspace_bytes": (_sz, [_i, _i, _i]),
     "slr_splat_workspace_init": (_i, [_vp, _sz, _i, _i, _i, _vp]),
     "slr_splat_bin": (_i, [_fp, _i, _i, _i, _vp, _sz, _vp]),

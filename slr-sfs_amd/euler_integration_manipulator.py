@@ -8,7 +8,7 @@ loop of ~15 torch kernels per step, euler_integration_manipulator.py:36-55).
 import torch
 import torch.nn as nn
 
-from ._lib import call, require_device
+from ._lib import call, lib, require_device
 
 
 def _steps(destination_frame):
@@ -130,6 +130,64 @@ class _EulerIntegrateBatch(torch.autograd.Function):
         grad_motion = torch.empty_like(motion)
         call("slr_euler_backward_batch", motion.device, motion, steps, b, height, width, 1.0, grad_disp, grad_motion)
         return grad_motion, None
+
+
+def _pair_forward(motion, steps_f, steps_p):
+    b, _, height, width = motion.shape
+    disp_f, disp_p = torch.empty_like(motion), torch.empty_like(motion)
+    call("slr_euler_pair_forward", motion.device, motion, steps_f, steps_p, b, height, width, disp_f, disp_p, None, None)
+    return disp_f, disp_p
+
+
+class _EulerIntegratePair(torch.autograd.Function):
+    """Both directions of the training step as one node: one launch forward, and a backward whose sum does not depend on the order
+    in which the contributions arrive (csrc/euler.hip: 64-bit fixed point) -- the same bits from run to run."""
+
+    @staticmethod
+    def forward(ctx, motion, steps_f, steps_p):
+        ctx.save_for_backward(motion, steps_f, steps_p)
+        return _pair_forward(motion, steps_f, steps_p)
+
+    @staticmethod
+    def backward(ctx, grad_f, grad_p):
+        motion, steps_f, steps_p = ctx.saved_tensors
+        grad_f = torch.zeros_like(motion) if grad_f is None else grad_f.contiguous()
+        grad_p = torch.zeros_like(motion) if grad_p is None else grad_p.contiguous()
+        require_device(grad_f, grad_p)
+        b, _, height, width = motion.shape
+        grad_motion = torch.empty_like(motion)
+        nbytes = int(lib().slr_euler_pair_workspace_bytes(b, height, width))
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=motion.device)
+        call("slr_euler_pair_backward", motion.device, motion, steps_f, steps_p, b, height, width, grad_f, grad_p, grad_motion, ws,
+             nbytes)
+        return grad_motion, None, None
+
+
+def euler_integration_pair(motion, steps_f, steps_p):
+    """(EulerIntegration(motion, steps_f), EulerIntegration(-motion, steps_p)) of the training step
+    (animating_softmax_splating.py:579-580), bit for bit, without the negation and in one launch; one autograd node whose gradient
+    w.r.t. `motion` is reproducible bit for bit.  motion [B,2,H,W] float32 on the device, contiguous; steps_f / steps_p: B step
+    counts each (a tensor, kept on the device, or a sequence of ints).  -> (flow_f, flow_p), both [B,2,H,W]."""
+    if not torch.is_tensor(motion):
+        raise TypeError(f"slr_sfs_amd.euler_integration_pair: a tensor is required, got {type(motion).__name__}")
+    if motion.dtype != torch.float32:
+        raise TypeError(f"slr_sfs_amd: float32 tensors required, got {motion.dtype}")
+    if motion.dim() != 4 or motion.shape[1] != 2 or min(motion.shape) < 1:
+        raise ValueError(f"euler_integration_pair: motion [B,2,H,W] with B, H, W >= 1 required, got {tuple(motion.shape)}")
+    if not motion.is_contiguous():
+        raise ValueError("euler_integration_pair: motion is not contiguous")
+    batch = motion.shape[0]
+    for name, s in (("steps_f", steps_f), ("steps_p", steps_p)):
+        count = s.numel() if torch.is_tensor(s) else len(s)
+        if count != batch:
+            raise ValueError(f"euler_integration_pair: {name} has {count} step counts for a batch of {batch}")
+    if not motion.is_cuda:                              # (last, so that every other refusal can be met without a device)
+        raise NotImplementedError("slr_sfs_amd operators run on ROCm device tensors only (no CPU path)")
+    steps_f = _steps_on_device(steps_f, batch, motion.device)
+    steps_p = _steps_on_device(steps_p, batch, motion.device)
+    if torch.is_grad_enabled() and motion.requires_grad:
+        return _EulerIntegratePair.apply(motion, steps_f, steps_p)
+    return _pair_forward(motion, steps_f, steps_p)
 
 
 class EulerIntegration(nn.Module):

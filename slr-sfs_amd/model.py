@@ -10,6 +10,8 @@ spectrally normalised tensors runs with the deferred weight gradient (``spectral
 per network forward's backward.  Nothing in a forward or in a whole iteration synchronises the host when the batch is on the device.
 There is no fallback: CPU tensors raise.
 """
+import copy
+
 import torch
 from torch import nn
 
@@ -97,7 +99,7 @@ class TrainingModel(nn.Module):
 
     def __init__(self, opts, vgg=None, *, encoder_widths=None, decoder_widths=None, decoder_updown=None, deterministic=False):
         super().__init__()
-        check_options(opts)
+        self._check_options(opts)
         self.opt = opts
         feat = int(_value(opts, "out_channel", _value(opts, "ngf", 64)))
         self.encoder = TrainableEncoderWithZ(cin=3, feat=feat, widths=encoder_widths, spectral=True)
@@ -113,6 +115,8 @@ class TrainingModel(nn.Module):
                                                               int(_value(opts, "voxel_size", 64))))
         self.relu_z = "relu" in str(_value(opts, "Z_model", "encoder"))
         self.defer_weight_grad(True)
+
+    _check_options = staticmethod(check_options)             # (JointTrainingModel: check_joint_options)
 
     def defer_weight_grad(self, on=True):
         """One list-wide weight-gradient pair per network forward's backward (default), or the per-layer pairs."""
@@ -166,18 +170,25 @@ class TrainingModel(nn.Module):
         end_fs, Z_p = self.encoder(end_img, noise=noise.get("end"))
         if self.relu_z:                                                                           # :488-490
             Z_f, Z_p = torch.relu(Z_f), torch.relu(Z_p)
-        if motions.shape[1] == 2:                                                                 # :538-546
-            flow = motions
-        else:
-            flow = motions[:, :2, ...].clone()
-            flow = flow * motions[:, 2:3, ...]
+        flow, motion_out = self._motion(batch, start_img, motions, bs, W)                          # :514-546
         flow = flow.reshape(bs, 2, W, W).contiguous()                                             # :578
         gen_fs = self.synthesis(start_fs, Z_f, end_fs, Z_p, flow, start_index, middle_index, end_index)   # :579-692
         gen_img = self.projector(gen_fs.contiguous(), noise=noise.get("projector"))               # :742
         gen_img = torch.tanh(gen_img)                                                             # :744
         loss = self.loss_function(gen_img, middle_img)                                            # :746
         pred_dict = {"OutputImg": middle_img, "PredImg": gen_img, "Z_f": self._z_f_norm(Z_f, start_fs), "GTMotion": flow}     # :755-762
+        if motion_out is not None:
+            self._add_motion(loss, pred_dict, motion_out)                                         # :748-753, :764-766
         return loss, pred_dict
+
+    def _motion(self, batch, start_img, motions, bs, W):
+        """The flow the integration gets (:538-546: the batch's motion) and what the subclass's regressor returned (None here)."""
+        if motions.shape[1] == 2:
+            flow = motions
+        else:
+            flow = motions[:, :2, ...].clone()
+            flow = flow * motions[:, 2:3, ...]
+        return flow, None
 
     @torch.no_grad()
     def _z_f_norm(self, Z_f, start_fs):
@@ -255,6 +266,142 @@ class TrainingModel(nn.Module):
         return self
 
 
+MOTION_MODEL_TYPE = "SPADE_unet_mask_motion"
+_SPADE_ORDER = ("", "2_0", "2_1", "4_0", "4_1", "8_0", "8_1", "8_2", "8_3", "8_4", "8_5", "8_6", "8_7")      # architectures.py:655-667
+
+
+def _with(opts, **kw):
+    """A shallow copy of the options (a Namespace or a dict) with ``kw`` set."""
+    new = copy.copy(opts)
+    for k, v in kw.items():
+        if isinstance(new, dict):
+            new[k] = v
+        else:
+            setattr(new, k, v)
+    return new
+
+
+def check_joint_options(opts):
+    """``JointTrainingModel``'s options: ``train_motion`` with ``motion_model_type SPADE_unet_mask_motion`` (the three-channel ``uvm``
+    predictors and every other type raise NotImplementedError naming the option), ``motionW`` = ``motionH`` = ``W`` (the reference's
+    ``flow_uvm.view(bs, 2, W, W)`` fails otherwise, animating_softmax_splating.py:526), and everything ``check_options`` refuses.  What
+    ``MotionTrainingModel`` refuses it refuses when it is built."""
+    if not _flag(opts, "train_motion"):
+        raise NotImplementedError("slr_sfs_amd.JointTrainingModel: option train_motion is required (without it: TrainingModel)")
+    kind = str(_value(opts, "motion_model_type", MOTION_MODEL_TYPE))
+    if kind != MOTION_MODEL_TYPE:
+        raise NotImplementedError(f"slr_sfs_amd.JointTrainingModel: option motion_model_type={kind} is not implemented (only {MOTION_MODEL_TYPE}"
+                                  f"{'; three-channel uvm predictions are not built' if 'uvm' in kind else ''})")
+    W = int(_value(opts, "W", 256))
+    for name in ("motionW", "motionH"):
+        if int(_value(opts, name, W)) != W:
+            raise NotImplementedError(f"slr_sfs_amd.JointTrainingModel: option {name}={_value(opts, name, W)} differs from W={W} (the reference's "
+                                      f"view(bs, 2, W, W) of the predicted motion fails there, too)")
+    check_options(_with(opts, train_motion=False))
+
+
+class JointTrainingModel(TrainingModel):
+    """``AnimatingSoftmaxSplating`` under ``--train_motion --motion_model_type SPADE_unet_mask_motion``
+    (train_animating_fixedMotion_finetuneFluid_IGANonly.sh): the frame synthesis trained on the motion the motion network PREDICTS.
+    ``motion_regressor`` is ``MotionTrainingModel(opts with model_type = motion_model_type)`` (:189-193), called on {"images": [start],
+    "motions", "hints"} between the encoder and the integration (:514-536); the flow is its ``PredMotion`` WITHOUT ``div_flow``, times
+    [W / motionW, W / motionH] (= 1: the sizes are required equal); ``Total Loss`` gains the motion model's, its named losses are copied
+    in, and pred_dict gains ``PredMotion`` and takes the motion model's ``GTMotion`` (:748-766).  batch: ``TrainingModel``'s with
+    ``motions`` [B,2,W,W] the ground truth and ``hints`` [B,2,W,W].
+
+    Both integrations run through ``euler_integration_pair``: with ``deterministic=True`` the gradient that reaches the motion network is
+    the same bits from run to run as well.  ``load_motion_regressor`` takes a motion checkpoint of ``train_motion_unet.py``
+    under the renamed keys, ``freeze_motion`` stops its parameters learning (both before the trainer's first step).  ``nf``: another width
+    of the motion network than the reference's 32 (tests)."""
+
+    _check_options = staticmethod(check_joint_options)
+
+    def __init__(self, opts, vgg=None, *, nf=32, encoder_widths=None, decoder_widths=None, decoder_updown=None, deterministic=False):
+        super().__init__(opts, vgg, encoder_widths=encoder_widths, decoder_widths=decoder_widths, decoder_updown=decoder_updown,
+                         deterministic=deterministic)
+        from .motion_training import MotionTrainingModel
+        self.synthesis = TrainingSynthesis(opts, deterministic=deterministic, euler_pair=True)
+        self.motion_regressor = MotionTrainingModel(_with(opts, model_type=_value(opts, "motion_model_type", MOTION_MODEL_TYPE)), nf=nf)
+
+    def _batch(self, batch):
+        if "hints" not in batch:                              # (before anything else: no device is needed to say so)
+            raise KeyError("slr_sfs_amd.JointTrainingModel: batch['hints'] is required (option use_hint_as_motion_input)")
+        out = super()._batch(batch)
+        if out[1].shape[1] != 2:
+            raise NotImplementedError("slr_sfs_amd.JointTrainingModel: three-channel uvm motions (motion_model_type) are not built")
+        return out
+
+    def _motion(self, batch, start_img, motions, bs, W):
+        motion_loss, out = self.motion_regressor({"images": [start_img], "motions": motions, "hints": batch["hints"]})   # :516-523
+        pred = out["PredMotion"]
+        if pred.shape[1] != 2:
+            raise NotImplementedError("slr_sfs_amd.JointTrainingModel: three-channel uvm predictions (motion_model_type) are not built")
+        # :524-535: PredMotion as it is (no div_flow), times [W / motionW, W / motionH] = [1, 1] (check_joint_options): the same bits
+        return pred.view(bs, 2, W, W), (motion_loss, out)
+
+    def _add_motion(self, loss, pred_dict, motion_out):
+        motion_loss, out = motion_out
+        # :751 is an in-place `+=` on the tensor under "Total Loss" -- which IS the first named loss's tensor when `losses` has one entry
+        # (SynthesisLoss leaves its first term unscaled), so that entry reads the new total as well.  Out of place here, same values.
+        old = loss["Total Loss"]
+        new = old + motion_loss["Total Loss"]
+        for k in list(loss):
+            if loss[k] is old:
+                loss[k] = new
+        for name in self.motion_regressor.loss_function.loss_names:                               # :752-753
+            loss[name] = motion_loss[name]
+        pred_dict["PredMotion"], pred_dict["GTMotion"] = out["PredMotion"], out["GTMotion"]       # :764-766
+
+    # ---- parameters and checkpoints
+    _MOTION = "motion_regressor.motion_predictor."
+
+    def load_motion_regressor(self, state_dict, prefix="model.module."):
+        """train_animating_fixmotion.py:438-446: the keys of a motion checkpoint that hold ``motion_predictor`` go under
+        ``motion_regressor.motion_predictor``; the others are not used.  Strict on the network: every tensor found, every key consumed."""
+        renamed = {k.replace("motion_predictor", self._MOTION[:-1]): v for k, v in state_dict.items() if "motion_predictor" in k}
+        self.motion_regressor.motion_predictor.load_reference_state_dict(renamed, prefix + self._MOTION)
+        return self
+
+    def freeze_motion(self):
+        """:448-450: the motion network's parameters stop learning (its u / v still move in train() mode, as the reference's do)."""
+        for name, p in self.motion_regressor.named_parameters():
+            if "motion_predictor" in name:
+                p.requires_grad = False
+        return self
+
+    def _reference_entries(self):
+        out = super()._reference_entries()
+        for k, t, sl in self.motion_regressor.motion_predictor._reference_entries():
+            out[self._MOTION + k] = t if sl is None else t[sl]
+        return out
+
+    def reference_parameters(self):
+        """The parent's rows with the motion network's between encoder and projector, in the reference's registration order; the rows
+        of ``mlp_gamma`` / ``mlp_beta`` carry the slice of ``mlp_gb`` they are.  learns: the parameter's ``requires_grad``."""
+        rows = super().reference_parameters()
+        net, mine = self.motion_regressor.motion_predictor, []
+        for name in [f"conv{i}" for i in range(1, 9)] + [f"dconv{i}" for i in range(1, 9)]:
+            m = getattr(net, name)
+            mine += [(f"{name}.bias", m.bias, m.bias.requires_grad), (f"{name}.weight_orig", m.weight_orig, m.weight_orig.requires_grad)]
+        for s in _SPADE_ORDER:
+            sp = getattr(net, f"spade_layer{s}")
+            sh, gb, C = sp.mlp_shared, sp.mlp_gb, sp.C
+            mine += [(f"spade_layer{s}.mlp_shared.0.weight", sh.weight, sh.weight.requires_grad),
+                     (f"spade_layer{s}.mlp_shared.0.bias", sh.bias, sh.bias.requires_grad)]
+            for half, sl in (("mlp_gamma", slice(0, C)), ("mlp_beta", slice(C, 2 * C))):
+                mine += [(f"spade_layer{s}.{half}.weight", gb.weight, gb.weight.requires_grad, sl),
+                         (f"spade_layer{s}.{half}.bias", gb.bias, gb.bias.requires_grad, sl)]
+        mine = [(self._MOTION + r[0],) + tuple(r[1:]) for r in mine]
+        cut = max(k for k, r in enumerate(rows) if r[0].startswith("encoder.")) + 1
+        return rows[:cut] + mine + rows[cut:]
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix="model.module."):
+        super().load_reference_state_dict(sd, prefix)                      # (checks every key and shape, the motion network's included)
+        self.motion_regressor.motion_predictor.load_reference_state_dict(sd, prefix + self._MOTION)
+        return self
+
+
 class Trainer(nn.Module):
     """``BaseModel`` (models/base_model.py): ``model``, with ``opts.discriminator_losses != '0'`` the discriminator ``netD``
     (``DiscriminatorLoss``: gan_mode, lambda_feat, no_ganFeat_loss, ndf, output_nc read from ``opts``), and the optimisers of
@@ -276,13 +423,16 @@ class Trainer(nn.Module):
                                           no_ganFeat_loss=bool(_flag(opts, "no_ganFeat_loss")), ndf=int(_value(opts, "ndf", 64)),
                                           output_nc=int(_value(opts, "output_nc", 3)))
         self.normalize_image = _flag(opts, "normalize_image")
-        self._optimizers = None
+        self._optimizers, self._rows = None, None
 
     # ---- optimisers (base_model.py:15-46, 80-93)
     @property
     def optimizers(self):
         if self._optimizers is None:
-            params = [t for _, t, learns in self.model.reference_parameters() if learns]
+            params, self._rows = [], self._reference_rows()                                       # (learns is read ONCE, here)
+            for _, t, learns, _ in self._rows:
+                if learns and all(t is not q for q in params):                                    # (a tensor the reference holds in pieces: once)
+                    params.append(t)
             listed = {id(t) for t in params}
             left = [n for n, p in self.model.named_parameters() if p.requires_grad and id(p) not in listed]
             if left:
@@ -352,10 +502,25 @@ class Trainer(nn.Module):
             sd.update({"netD." + k: v.detach().clone() for k, v in self.netD.state_dict().items()})
         return sd
 
+    def _reference_rows(self):
+        """``model.reference_parameters()`` as (key, tensor, learns, rows): a fourth entry is the slice of ``tensor`` (along dimension 0)
+        that the reference holds as a parameter of its own -- the motion network's mlp_gamma / mlp_beta are the halves of one tensor."""
+        return [(r[0], r[1], r[2], r[3] if len(r) > 3 else None) for r in self.model.reference_parameters()]
+
     def _slots(self):
-        """Reference ``optimizerG`` index of each of this optimiser's parameters, and the reference's parameter count."""
-        rows = self.model.reference_parameters()
-        return [k for k, (_, _, learns) in enumerate(rows) if learns], len(rows)
+        """[(reference ``optimizerG`` index, index in this optimiser, slice or None)] of the rows that learn, and the reference's
+        parameter count.  Once the optimiser exists the rows are those it was made from: a parameter frozen then keeps its index and
+        has no state."""
+        rows = self._rows if self._optimizers is not None else self._reference_rows()
+        own, slots = [], []
+        for k, (_, t, learns, sl) in enumerate(rows):
+            if learns:
+                j = next((j for j, q in enumerate(own) if q is t), None)
+                if j is None:
+                    j = len(own)
+                    own.append(t)
+                slots.append((k, j, sl))
+        return slots, len(rows)
 
     def reference_checkpoint(self):
         """{"state_dict", "optimizerG", ["optimizerD"]}: the tensors under the reference's keys and the optimiser states under the
@@ -365,8 +530,12 @@ class Trainer(nn.Module):
         own = self.optimizers.state_dict()
         slots, n = self._slots()
         g = own["optimizerG"]
-        ckpt["optimizerG"] = {"state": {slots[k]: st for k, st in g["state"].items()},
-                              "param_groups": [dict(g["param_groups"][0], params=list(range(n)))]}
+        state = {}
+        for ref, j, sl in slots:
+            if j in g["state"]:
+                st = g["state"][j]
+                state[ref] = st if sl is None else dict(st, exp_avg=st["exp_avg"][sl].clone(), exp_avg_sq=st["exp_avg_sq"][sl].clone())
+        ckpt["optimizerG"] = {"state": state, "param_groups": [dict(g["param_groups"][0], params=list(range(n)))]}
         if self.use_discriminator:
             ckpt["optimizerD"] = own["optimizerD"]
         return ckpt
@@ -394,19 +563,35 @@ class Trainer(nn.Module):
                     raise ValueError(f"Trainer.load_reference_checkpoint: netD.{k}: shape {tuple(netd[k].shape)}, expected {tuple(t.shape)}")
         own = None
         if "optimizerG" in ckpt:
-            rows = self.model.reference_parameters()
             slots, n = self._slots()
+            rows = self._rows if self._optimizers is not None else self._reference_rows()
             g = ckpt["optimizerG"]
             if len(g["param_groups"]) != 1 or len(g["param_groups"][0]["params"]) != n:
                 raise ValueError(f"Trainer.load_reference_checkpoint: optimizerG lists {sum(len(q['params']) for q in g['param_groups'])} parameters "
                                  f"in {len(g['param_groups'])} group(s), the reference's model has {n} in one")
-            back = {ref: k for k, ref in enumerate(slots)}
+            back = {ref: (j, sl) for ref, j, sl in slots}
             stray = sorted(k for k in g["state"] if k not in back)
             if stray:
                 raise ValueError(f"Trainer.load_reference_checkpoint: optimizerG has state for frozen parameters {stray[:4]}")
-            self._check_moments("optimizerG", g["state"], {k: rows[k][1] for k in back})
-            own = {"optimizerG": {"state": {back[k]: st for k, st in g["state"].items()},
-                                  "param_groups": [dict(g["param_groups"][0], params=list(range(len(slots))))]}}
+            self._check_moments("optimizerG", g["state"], {k: rows[k][1] if back[k][1] is None else rows[k][1][back[k][1]] for k in back})
+            merged, pieces = {}, {}
+            for ref, j, sl in slots:
+                if sl is None:
+                    if ref in g["state"]:
+                        merged[j] = g["state"][ref]
+                else:
+                    pieces.setdefault(j, []).append((sl.start, ref))
+            for j, parts in pieces.items():                                                       # the pieces of one tensor: all or none, one step
+                have = [ref for _, ref in sorted(parts) if ref in g["state"]]
+                if not have:
+                    continue
+                if len(have) != len(parts) or any(float(g["state"][r]["step"]) != float(g["state"][have[0]]["step"]) for r in have):
+                    raise ValueError(f"Trainer.load_reference_checkpoint: optimizerG states {[r for _, r in sorted(parts)]} are the pieces of one "
+                                     f"tensor here: all of them are needed, at one step count")
+                merged[j] = dict(g["state"][have[0]], exp_avg=torch.cat([g["state"][r]["exp_avg"] for r in have]),
+                                 exp_avg_sq=torch.cat([g["state"][r]["exp_avg_sq"] for r in have]))
+            own = {"optimizerG": {"state": merged,
+                                  "param_groups": [dict(g["param_groups"][0], params=list(range(1 + max((j for _, j, _ in slots), default=-1))))]}}
             if self.use_discriminator:
                 if "optimizerD" not in ckpt:
                     raise KeyError("Trainer.load_reference_checkpoint: optimizerG without optimizerD (this trainer has a discriminator)")

@@ -11,7 +11,7 @@ import math
 import torch
 
 from ._lib import BLEND_DETERMINISTIC, WS_CLEAN, call, lib, require_device, workspace
-from .euler_integration_manipulator import EulerIntegration
+from .euler_integration_manipulator import EulerIntegration, euler_integration_pair
 
 _UNSUPPORTED = ("use_softmax_splatter_v2", "use_softmax_splatter_v3", "use_3d_splatter", "use_mesh_splatter", "random_ff_mask")
 
@@ -167,12 +167,17 @@ class TrainingSynthesis(torch.nn.Module):
     """The reference's forward() from the Euler integration to the normalised features (animating_softmax_splating.py:577-692):
     forward(start_fs, Z_f, end_fs, Z_p, motion, start_index, middle_index, end_index) -> [B,C,H,W], differentiable in the features, the
     logits and the motion field, without a host synchronisation when the indices are device tensors.  With ``train_Z`` off Z_f / Z_p are
-    ignored (the reference replaces them by ones, whose weights cancel).  ``deterministic``: passed on to ``splat_blend``."""
+    ignored (the reference replaces them by ones, whose weights cancel).  ``deterministic``: passed on to ``splat_blend``.
+    ``euler_pair``: both integrations through ``euler_integration_pair`` -- the same flows bit for bit, one launch, and a gradient
+    w.r.t. the motion field that is the same bits from run to run (for a motion field that is itself being trained)."""
 
-    def __init__(self, opts=None, deterministic=False):
+    def __init__(self, opts=None, deterministic=False, euler_pair=False):
         super().__init__()
         if not isinstance(deterministic, bool):
             raise TypeError(f"slr_sfs_amd.TrainingSynthesis: deterministic must be a bool, got {type(deterministic).__name__}")
+        if not isinstance(euler_pair, bool):
+            raise TypeError(f"slr_sfs_amd.TrainingSynthesis: euler_pair must be a bool, got {type(euler_pair).__name__}")
+        self.euler_pair = euler_pair
         self.opts = opts
         self.deterministic = deterministic
         self.options = _blend_options(opts)
@@ -182,8 +187,12 @@ class TrainingSynthesis(torch.nn.Module):
         bs = start_fs.shape[0]
         dev = start_fs.device
         start_index, middle_index, end_index = (torch.as_tensor(v, device=dev) for v in (start_index, middle_index, end_index))
-        flow_f = self.euler_integration(motion, middle_index.long() - start_index.long())                      # :579
-        flow_p = self.euler_integration(-motion, end_index.long() + 1 - middle_index.long())                   # :580
+        if self.euler_pair:
+            flow_f, flow_p = euler_integration_pair(motion.contiguous(), (middle_index.long() - start_index.long()).reshape(-1)[:bs],
+                                                    (end_index.long() + 1 - middle_index.long()).reshape(-1)[:bs])   # :579-580
+        else:
+            flow_f = self.euler_integration(motion, middle_index.long() - start_index.long())                  # :579
+            flow_p = self.euler_integration(-motion, end_index.long() + 1 - middle_index.long())               # :580
         alpha = (1.0 - (middle_index.float() - start_index.float()).float() / (
             end_index.float() - start_index.float() + 1.0).float()).reshape(bs).contiguous()                   # :585-586
         if not self.options["train_z"]:
