@@ -93,7 +93,7 @@ int slr_euler_integrate_batch(const float *motion, const long long *steps, int B
                               float *disp, float *visible, void *stream);
 
 /* Gradient of slr_euler_integrate_batch w.r.t. the motion fields (per sample: slr_euler_backward).
- *   grad_disp [B,2,H,W] in;  grad_motion [B,2,H,W] out (zeroed here) */
+ *   grad_disp [B,2,H,W] in;  grad_motion [B,2,H,W] out (zeroed here).  Sizes: B < 65536, H*W < 2^30, B*H*W < 2^38 - 128. */
 int slr_euler_backward_batch(const float *motion, const long long *steps, int B, int H, int W, float sign,
                              const float *grad_disp, float *grad_motion, void *stream);
 
@@ -366,7 +366,8 @@ int slr_max_warp_norm(const float *in, const float *flow, float *scratch, float 
  * models/layers/normalization.py:219-231 + blocks.py:229-231 + partialconv2d.py:69.
  *   mask_channels = 1: mask [N,1,H,W];  = C: mask [N,C,H,W];  = 0: mask = (x != 0)
  *   (models/networks/architectures.py:369);  = -1: no mask (plain BN + ReLU of the encoder /
- *   background blocks, blocks.py:66-74).  `mask` is ignored for 0 and -1. */
+ *   background blocks, blocks.py:66-74).  `mask` is ignored for 0 and -1.
+ *   Sizes: N, C <= 65535, H*W < 2^31 - 2^18 (a plane is walked in steps of up to 1024 workgroups of 256). */
 int slr_bn_relu_mask(const float *x, const float *scale, const float *shift, const float *mask,
                      int mask_channels, float *y, int N, int C, int H, int W, void *stream);
 
@@ -379,7 +380,8 @@ int slr_bn_relu_mask(const float *x, const float *scale, const float *shift, con
  *                       partial convolution of the block, blocks.py:233-236 / partialconv2d.py:69).
  * Replaces models/layers/partialconv2d.py:64-74.
  *   raw0 [N,C,H,W]; mask_box [N,1,H,W]; residual [N,C,H,W] or NULL; next_scale/next_shift [C] or
- *   NULL (exclusive with residual); um_out [N,1,H,W] or NULL receives um; winsize = Cin*k*k. */
+ *   NULL (exclusive with residual); um_out [N,1,H,W] or NULL receives um; winsize = Cin*k*k.
+ *   Sizes: N, C <= 65535, H*W < 2^31 - 2^18. */
 int slr_pconv_epilogue(const float *raw0, const float *bias, const float *mask_box, float mask_scale,
                        const float *residual, const float *next_scale, const float *next_shift,
                        float *out, float *um_out, float winsize, int N, int C, int H, int W, void *stream);
@@ -416,7 +418,8 @@ int slr_conv_saturation_record(unsigned *host_slot, void *stream);
  * (channels are zero-padded to multiples of 16 / 32 inside the weight buffer).
  *   Weights are prepared once per layer with slr_conv3x3_split_weights into a buffer of
  *   slr_conv3x3_weight_bytes(Cout, Cin) bytes; `wscale` is a power of two that brings max|w|
- *   near 2^12 (f16 range) and must be passed unchanged to the forward calls. */
+ *   near 2^12 (f16 range) and must be passed unchanged to the forward calls.  A weight buffer (3x3, 1x1, Winograd) holds fewer than
+ *   2^30 - 256 padded elements. */
 /* `layout` flags of the forward calls: the activation BETWEEN two of these kernels may be kept channel-blocked,
  * [N, C/8, H, W, 8] instead of [N, C, H, W] (C % 8 == 0): the consumer then stages an item's 8 channels with two
  * 16-byte loads instead of eight 4-byte loads, the producer stores 16 bytes per lane without a transpose.
@@ -455,7 +458,9 @@ int slr_conv3x3_wino_weights(const float *w /* [Cout,Cin,3,3] */, void *wfrag /*
 /* out = conv3x3(pre(in)) + bias + residual, pre(x) = relu(x*pre_scale[c] - pre_shift[c]) when pre_scale
  * is given (eval-mode noise-BN + ReLU in front of the convolution, models/layers/blocks.py:66-74 +
  * normalization.py:219-231), identity otherwise.  bias [Cout] or NULL; residual [N,Cout,H,W] or NULL
- * (the x_a + x_b of ResNet_Block, blocks.py:87). */
+ * (the x_a + x_b of ResNet_Block, blocks.py:87).
+ * Sizes of every 3x3 entry point: N < 65536, Cout < 2^20, Cin*H*W < 2^31 (a sample's input is indexed with 32 bits), H*W < 2^31 - 1024,
+ * N*Cout*H*W < 2^40 (offsets of samples and of output planes are 64-bit); a batch may hold more than 2^31 elements. */
 int slr_conv3x3_forward(const float *in, const void *wsplit, const float *bias, const float *residual, float *out,
                         int N, int Cin, int Cout, int H, int W, float wscale, float xscale,
                         const float *pre_scale, const float *pre_shift, int layout, void *stream);
@@ -493,7 +498,8 @@ int slr_pconv3x3_forward(const float *x, const float *pre_scale, const float *pr
  * um_out stays full resolution.  A wave pools the 4 x 16 pixels of its tile in registers; the pooled pixels that need the row above /
  * the column left of the tile are completed by a small second launch from side buffers in pool_ws (slr_conv_pool_ws_bytes: the last row
  * of every tile row and the last column of every tile column, ~16 % of the full-resolution tensor).  Same 9 terms per pooled pixel as
- * slr_avgpool3x3s2, summed rows first: equal to the two-kernel form to fp32 rounding.  pool_ws = NULL otherwise. */
+ * slr_avgpool3x3s2, summed rows first: equal to the two-kernel form to fp32 rounding.  pool_ws = NULL otherwise.
+ * Both resampling epilogues: N * Cout / 8 <= 65535 (the second launch has one grid row per sample and 8-channel group). */
 size_t slr_conv_pool_ws_bytes(int N, int Cout, int H, int W);
 /* With SLR_CONV_UP_OUT (same conditions) the "Up" block's nn.Upsample(scale_factor=2, mode='bilinear') (blocks.py:200-203) happens in the
  * epilogue: a tile's 8 x 32 pixels give the 16 x 64 output pixels below them; all but the first / last row and column of that block come
@@ -544,7 +550,7 @@ int slr_pconv3x3_forward_skipout(const float *x, const float *pre_scale, const f
  *     then the partial epilogue of the <= 4-channel kernel operation for operation with `mask` [N,1,H,W] (the wide kernel's um_out) and
  *     Cin input channels behind every mask value: out [N,3,H,W] = relu(((raw * ratio + bias) * um) * next_scale - next_shift) * um
  *     (next_scale = NULL: without), um_out [N,1,H,W], skip_out [N,3,H,W] = Z[27 + co] (+ skip_bias): what slr_pconv3x3_forward_skipout
- *     returns, to the rounding of a different order of the same sums. */
+ *     returns, to the rounding of a different order of the same sums.  Sizes: N < 65536, H*W < 2^31 - 64, H <= 262140. */
 size_t slr_conv_tail_weight_bytes(int Cin);
 int slr_conv_tail_weight_source(int Cin, int element, int *operand, int *half, int *row, int *ci);
 int slr_conv_tail_weights(const float *w_aa, const float *w_b, void *wtail, int Cin, float wscale_aa, float wscale_b, void *stream);
@@ -557,7 +563,8 @@ int slr_narrow_gather(const float *z, const float *mask, const float *bias, cons
 
 /* 1x1 convolution (skip branch of the residual blocks, models/layers/blocks.py:192-193,243-247) on the same
  * split-f16 arithmetic: out = conv1x1(in) + bias.  HBM-bound, no LDS.  Weights prepared once per layer with
- * slr_conv1x1_split_weights into slr_conv1x1_weight_bytes(Cout, Cin) bytes; wscale as for the 3x3 kernel. */
+ * slr_conv1x1_split_weights into slr_conv1x1_weight_bytes(Cout, Cin) bytes; wscale as for the 3x3 kernel.
+ * Sizes: N < 65536, Cout < 2^20, H*W < 2^31 - 128, Cin*H*W < 2^40: one sample may hold more than 2^31 elements. */
 size_t slr_conv1x1_weight_bytes(int Cout, int Cin);
 int slr_conv1x1_split_weights(const float *w /* [Cout,Cin,1,1] */, void *wsplit, int Cout, int Cin,
                               float wscale, void *stream);
@@ -569,18 +576,18 @@ int slr_conv1x1_forward(const float *in, const void *wsplit, const float *bias /
 /* ------------------------------------------------------------------ decoder resampling stages (8 f3) */
 
 /* nn.AvgPool2d(3, stride=2, padding=1) (count_include_pad): "Down" of models/layers/blocks.py:196-199.
- *   in [N,C,H,W] -> out [N,C,(H-1)/2+1,(W-1)/2+1] */
+ *   in [N,C,H,W] -> out [N,C,(H-1)/2+1,(W-1)/2+1].  Sizes: N*C < 65536, H*W < 2^30. */
 int slr_avgpool3x3s2(const float *in, float *out, int N, int C, int H, int W, int b8 /* both tensors channel-blocked */,
                      void *stream);
 
 /* nn.Upsample(scale_factor=2, mode='bilinear') (align_corners=False): "Up" of blocks.py:200-203.
- *   in [N,C,H,W] -> out [N,C,2H,2W] */
+ *   in [N,C,H,W] -> out [N,C,2H,2W].  Sizes: N*C < 65536, H*W < 2^28 (the output plane is indexed with an int). */
 int slr_upsample_bilinear2x(const float *in, float *out, int N, int C, int H, int W, int b8 /* both tensors channel-blocked */,
                             void *stream);
 
 /* 1x1 convolution onto 1..4 output channels (the skip branch of the decoder's last block,
  * blocks.py:192-193,243-247 with configs.py:117-137): out = bias + w . in;  w [Cout,Cin], bias [Cout] or NULL.
- *   NCHW input requires H*W % 4 == 0 and 16-byte aligned tensors. */
+ *   NCHW input requires H*W % 4 == 0 and 16-byte aligned tensors.  Sizes: N < 65536, H*W < 2^31 - 256, Cout*Cin < 2^31. */
 int slr_conv1x1_small(const float *in, const float *w, const float *bias, float *out,
                       int N, int Cin, int Cout, int H, int W, int in_b8 /* `in` channel-blocked; `out` is always NCHW */,
                       void *stream);
@@ -608,13 +615,14 @@ int slr_instnorm_spade(const float *x, const float *gamma_beta, float *out, int 
 
 /* The segmap of a SPADE layer (networks.py:446-457): F.interpolate(in, size=(H >> k, W >> k)) per channel, bilinear
  * (align_corners=False) for every channel but `nearest_channel` (the mask: mode='nearest'; -1 = none).  in [N,C,H,W] ->
- * out [N,C,H>>k,W>>k]; H and W multiples of 2^k. */
+ * out [N,C,H>>k,W>>k]; H and W multiples of 2^k, k < 16.  Sizes: N*C < 65536, H*W < 2^31 - 256. */
 int slr_resize_segmap(const float *in, float *out, int N, int C, int H, int W, int k, int nearest_channel, void *stream);
 
 /* The decoders' x2 up-sampling + skip concatenation: out[n] = cat(up(a[n]), up(b[n])) [N,Ca+Cb,2H,2W] with a [N,Ca,H,W], b [N,Cb,H,W]
  * (Cb = 0: a alone).  up = nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False) (the expression of
  * slr_upsample_bilinear2x) except channel `nearest_channel` of EACH source, which is nearest (architectures.py:712-740; -1 = none).
- * relu = 1: ReLU of the inputs (up(relu(cat)), architectures.py:463-489 and e8 at :710); 2: ReLU of the output (:715-741); 0: none. */
+ * relu = 1: ReLU of the inputs (up(relu(cat)), architectures.py:463-489 and e8 at :710); 2: ReLU of the output (:715-741); 0: none.
+ * Sizes: N*(Ca+Cb) < 65536, 4*H*W < 2^31 - 256 (the output plane is indexed with an int). */
 int slr_upsample2x_concat(const float *a, int Ca, const float *b, int Cb, float *out, int N, int H, int W, int nearest_channel, int relu,
                           void *stream);
 
@@ -629,7 +637,7 @@ int slr_upsample2x_concat(const float *a, int Ca, const float *b, int Cb, float 
  * evaluation/animation/metrics.py:psnr in ONE pass: out [N,2] = per image (ssim, mse).  mask [N,1,H,W] or NULL: with a mask
  * ssim = sum(mask * mean_c(ssim_map)) / max(sum(mask), 1) (ssim.py:61-67) and mse = sum(mask * err^2) / (3 max(sum(mask), 1))
  * (metrics.py:12-17); without, both are means over C, H, W (ssim.py:76, metrics.py:20).  ws: slr_ssim_ws_bytes(N, H, W) bytes,
- * 8-byte aligned (per-tile partial sums). */
+ * 8-byte aligned (per-tile partial sums).  Sizes: N < 65536, C <= 64, H*W < 2^31 - 128, N*C*H*W < 2^40. */
 size_t slr_ssim_ws_bytes(int N, int H, int W);
 int slr_ssim_mse(const void *img1, const void *img2, int u8, const float *mask, float *out, int N, int C, int H, int W,
                  int window_size, void *ws, size_t ws_bytes, void *stream);
@@ -705,7 +713,8 @@ size_t slr_conv3x3_grad_ws_bytes(int N, int Cin, int Cout, int H, int W, int spl
  *   dw[co][ci][ky][kx] = sum_{n,y,x} g[n,co,y,x] * x[n,ci,y+ky-1,x+kx-1] (zero padding), plain [Cout,Cin,3,3];  db[co] = sum g[n,co,y,x].
  * x [N,Cin,H,W], g [N,Cout,H,W]; any Cin, Cout, H, W >= 1.  fp32 products and sums on v_mfma_f32_32x32x2_f32 inside a slab of pixels, the
  * slabs added in double in a fixed order; db in double throughout.  splits: 0 = the library's choice, > 0 = that many slabs (at most one
- * per chunk).  layout: SLR_GRAD_X_B8 | SLR_GRAD_G_B8.  db may be NULL.  ws: 256-byte aligned, else SLR_E_WORKSPACE. */
+ * per chunk).  layout: SLR_GRAD_X_B8 | SLR_GRAD_G_B8.  db may be NULL.  ws: 256-byte aligned, else SLR_E_WORKSPACE.
+ * Sizes of both calls: N * max(Cin, Cout) * H * W < 2^31 - 1024, N * Cout <= 65535, channels <= 65535 * 64, 9 * Cout * Cin < 2^31 - 64. */
 int slr_conv3x3_weight_grad(const float *x, const float *g, float *dw, float *db, int N, int Cin, int Cout, int H, int W,
                             int splits, int layout, void *ws, size_t ws_bytes, void *stream);
 

@@ -1461,28 +1461,29 @@ static int conv_not_built() {
     return SLR_E_BADARG;
 }
 
-static int check_xscale(float xscale) {
+static int check_xscale(const char *fn, float xscale) {
     int ex = 0;
-    SLR_CHECK_ARG(xscale > 0.0f && xscale <= CV_XSCALE && frexpf(xscale, &ex) == 0.5f, "xscale: a power of two in (0, 64]");
+    SLR_CHECK_ARG_FN(fn, xscale > 0.0f && xscale <= CV_XSCALE && frexpf(xscale, &ex) == 0.5f, "xscale: a power of two in (0, 64]");
     return 0;
 }
 
-static int conv_check_layout(int layout, const void *in, const void *out, int Cin, int Cout, const void *residual,
+static int conv_check_layout(const char *fn, int layout, const void *in, const void *out, int Cin, int Cout, const void *residual,
                              bool derived_mask) {
     layout &= ~(SLR_CONV_F32 | SLR_CONV_WINO | SLR_CONV_SKIP_B8 | SLR_CONV_POOL_OUT | SLR_CONV_UP_OUT);      // (the last three: conv_set_skip)
-    SLR_CHECK_ARG((layout & ~(SLR_CONV_IN_B8 | SLR_CONV_OUT_B8 | SLR_CONV_RES_B8)) == 0, "layout flags");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_RES_B8) || ((layout & SLR_CONV_OUT_B8) && residual && !((uintptr_t)residual & 15)),
+    SLR_CHECK_ARG_FN(fn, (layout & ~(SLR_CONV_IN_B8 | SLR_CONV_OUT_B8 | SLR_CONV_RES_B8)) == 0, "layout flags");
+    SLR_CHECK_ARG_FN(fn, !(layout & SLR_CONV_RES_B8) || ((layout & SLR_CONV_OUT_B8) && residual && !((uintptr_t)residual & 15)),
                   "a channel-blocked residual goes with a channel-blocked output");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_IN_B8) || (Cin % 8 == 0 && !((uintptr_t)in & 15) && !derived_mask),
+    SLR_CHECK_ARG_FN(fn, !(layout & SLR_CONV_IN_B8) || (Cin % 8 == 0 && !((uintptr_t)in & 15) && !derived_mask),
                   "channel-blocked input needs Cin % 8 == 0, a 16-byte aligned tensor and an explicit mask");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_OUT_B8) || (Cout % 8 == 0 && !((uintptr_t)out & 15)),
+    SLR_CHECK_ARG_FN(fn, !(layout & SLR_CONV_OUT_B8) || (Cout % 8 == 0 && !((uintptr_t)out & 15)),
                   "channel-blocked output needs Cout % 8 == 0 and a 16-byte aligned tensor");
     return 0;
 }
 
-static int conv_check_dims(int N, int Cin, int Cout, int H, int W) {
-    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && Cout > 0 && Cout < (1 << 20) && H > 0 && W > 0 &&
-                  (long long)Cin * H * W < (1LL << 31) && (long long)N * Cout * H * W < (1LL << 40), "sizes");
+static int conv_check_dims(const char *fn, int N, int Cin, int Cout, int H, int W) {
+    SLR_CHECK_ARG_FN(fn, N > 0 && N < 65536 && Cin > 0 && Cout > 0 && Cout < (1 << 20) && H > 0 && W > 0 &&
+                  (long long)Cin * H * W < (1LL << 31) && (long long)H * W < (1LL << 31) - 1024 &&
+                  (long long)N * Cout * H * W < (1LL << 40), "sizes");      // (H * W: a column or row past the last block's halo stays an int)
     return 0;
 }
 
@@ -1512,13 +1513,14 @@ SLR_EXPORT size_t slr_conv3x3_wino_weight_bytes(int Cout, int Cin) {
 enum WeightForm { WSPLIT, WF32, WWINO };
 // Cout, Cin: of the convolution the buffer serves.  scale (a device scalar or none) and backward (the source is the forward's weight
 // [Cin,Cout,k,k], read flipped and transposed): the fp32 rung only.
-static int conv_weights(WeightForm form, int taps, const float *w, void *buf, int Cout, int Cin, float wscale, void *stream,
+static int conv_weights(const char *fn, WeightForm form, int taps, const float *w, void *buf, int Cout, int Cin, float wscale, void *stream,
                         const float *scale = nullptr, int backward = 0) {
     static_assert(36 * sizeof(float) * 8 <= 32 * 16 * 9 * 2 * sizeof(_Float16), "8 input channels of plain weights fit 16 of the split layout");
-    SLR_CHECK_ARG(w && buf, "null pointer");
+    SLR_CHECK_ARG_FN(fn, w && buf, "null pointer");
     const int CoutP = form == WWINO ? wino_cout_pad(Cout) : taps == 9 ? conv_cout_pad(Cout) : conv1x1_cout_pad(Cout), CinP = conv_cin_pad(Cin);
-    SLR_CHECK_ARG(Cout > 0 && Cin > 0 && (long long)CoutP * CinP * (form == WWINO ? 16 : taps) < (1LL << 30), "sizes");
-    SLR_CHECK_ARG(form != WSPLIT || wscale > 0.0f, "wscale");
+    SLR_CHECK_ARG_FN(fn, Cout > 0 && Cin > 0 && (long long)CoutP * CinP * (form == WWINO ? 16 : taps) < (1LL << 30) - 256,
+                     "sizes");      // (the kernels' loops step by the whole grid, ceil(total / 256) * 256: the index that leaves them stays an int)
+    SLR_CHECK_ARG_FN(fn, form != WSPLIT || wscale > 0.0f, "wscale");
     hipStream_t st = (hipStream_t)stream;
     const int total = form == WWINO ? CoutP * CinP : CoutP * CinP * taps;
     if (form != WWINO && taps == 9 && Cout <= CF_MAXCO) {
@@ -1534,25 +1536,25 @@ static int conv_weights(WeightForm form, int taps, const float *w, void *buf, in
     } else {
         hipLaunchKernelGGL(conv_wino_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, (float *)buf, Cout, Cin, CoutP, CinP);
     }
-    SLR_CHECK_LAUNCH();
+    SLR_CHECK_HIP_FN(fn, hipGetLastError());
     return 0;
 }
 
 // ---- scaled preparation of the fp32 rung (ABI 20): one tensor, or every convolution of a network from a plan in device memory ----------
 
-static int conv_weights_scaled(int taps, const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
-    SLR_CHECK_ARG(scale, "null pointer (scale)");
-    SLR_CHECK_ARG(!(((uintptr_t)w | (uintptr_t)scale | (uintptr_t)wfrag) & 3), "4-byte aligned tensors");
-    return backward ? conv_weights(WF32, taps, w, wfrag, Cin, Cout, 1.0f, stream, scale, 1)
-                    : conv_weights(WF32, taps, w, wfrag, Cout, Cin, 1.0f, stream, scale, 0);
+static int conv_weights_scaled(const char *fn, int taps, const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
+    SLR_CHECK_ARG_FN(fn, scale, "null pointer (scale)");
+    SLR_CHECK_ARG_FN(fn, !(((uintptr_t)w | (uintptr_t)scale | (uintptr_t)wfrag) & 3), "4-byte aligned tensors");
+    return backward ? conv_weights(fn, WF32, taps, w, wfrag, Cin, Cout, 1.0f, stream, scale, 1)
+                    : conv_weights(fn, WF32, taps, w, wfrag, Cout, Cin, 1.0f, stream, scale, 0);
 }
 
 SLR_EXPORT int slr_conv3x3_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
-    return conv_weights_scaled(9, w, scale, wfrag, Cout, Cin, backward, stream);
+    return conv_weights_scaled(__func__, 9, w, scale, wfrag, Cout, Cin, backward, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_f32_weights_scaled(const float *w, const float *scale, void *wfrag, int Cout, int Cin, int backward, void *stream) {
-    return conv_weights_scaled(1, w, scale, wfrag, Cout, Cin, backward, stream);
+    return conv_weights_scaled(__func__, 1, w, scale, wfrag, Cout, Cin, backward, stream);
 }
 
 namespace slr {
@@ -1658,33 +1660,33 @@ SLR_EXPORT int slr_conv_prep_scaled_multi(const void *plan_dev, int n_tensors, i
 }
 
 SLR_EXPORT int slr_conv3x3_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
-    return conv_weights(WSPLIT, 9, w, wsplit, Cout, Cin, wscale, stream);
+    return conv_weights(__func__, WSPLIT, 9, w, wsplit, Cout, Cin, wscale, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_split_weights(const float *w, void *wsplit, int Cout, int Cin, float wscale, void *stream) {
-    return conv_weights(WSPLIT, 1, w, wsplit, Cout, Cin, wscale, stream);
+    return conv_weights(__func__, WSPLIT, 1, w, wsplit, Cout, Cin, wscale, stream);
 }
 
 SLR_EXPORT int slr_conv3x3_f32_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    return conv_weights(WF32, 9, w, wfrag, Cout, Cin, 1.0f, stream);
+    return conv_weights(__func__, WF32, 9, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_f32_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    return conv_weights(WF32, 1, w, wfrag, Cout, Cin, 1.0f, stream);
+    return conv_weights(__func__, WF32, 1, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
 SLR_EXPORT int slr_conv3x3_wino_weights(const float *w, void *wfrag, int Cout, int Cin, void *stream) {
-    return conv_weights(WWINO, 9, w, wfrag, Cout, Cin, 1.0f, stream);
+    return conv_weights(__func__, WWINO, 9, w, wfrag, Cout, Cin, 1.0f, stream);
 }
 
 SLR_EXPORT int slr_conv1x1_forward(const float *in, const void *wsplit, const float *bias, float *out, int N, int Cin,
                                    int Cout, int H, int W, float wscale, float xscale, int layout, void *stream) {
     SLR_CHECK_ARG(in && wsplit && out, "null pointer");
-    if (int e = check_xscale(xscale)) return e;
+    if (int e = check_xscale(__func__, xscale)) return e;
     const bool f32 = (layout & SLR_CONV_F32) != 0;
     SLR_CHECK_ARG(!f32 || (wscale == 1.0f && xscale == 1.0f), "the fp32 rung takes no operand scales (wscale = xscale = 1)");
     layout &= ~SLR_CONV_F32;
-    if (int e = conv_check_layout(layout & ~SLR_CONV_RES_B8, in, out, Cin, Cout, nullptr, false)) return e;
+    if (int e = conv_check_layout(__func__, layout & ~SLR_CONV_RES_B8, in, out, Cin, Cout, nullptr, false)) return e;
     SLR_CHECK_ARG(!(layout & SLR_CONV_RES_B8), "layout flags");
     SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && Cout > 0 && Cout < (1 << 20) && H > 0 && W > 0 &&
                   (long long)Cin * H * W < (1LL << 40) && (long long)H * W < (1LL << 31) - 128, "sizes");
@@ -1726,35 +1728,36 @@ SLR_EXPORT size_t slr_conv_up_ws_bytes(int N, int Cout, int H, int W) {
     return conv_pool_ws_bytes(N, Cout, H, W, true);
 }
 
-static int conv_set_skip(ConvArgs &a, const SkipOp *sk, float xscale, int &layout) {
+static int conv_set_skip(const char *fn, ConvArgs &a, const SkipOp *sk, float xscale, int &layout) {
     const int layout_in = layout;
     const bool sb8 = (layout & SLR_CONV_SKIP_B8) != 0, up = (layout & SLR_CONV_UP_OUT) != 0, pool = (layout & SLR_CONV_POOL_OUT) != 0 || up;
     layout &= ~(SLR_CONV_SKIP_B8 | SLR_CONV_POOL_OUT | SLR_CONV_UP_OUT);
-    if (!sk) { SLR_CHECK_ARG(!sb8 && !pool, "layout flags"); return 0; }
+    if (!sk) { SLR_CHECK_ARG_FN(fn, !sb8 && !pool, "layout flags"); return 0; }
     if (sk->skip_out) {
-        SLR_CHECK_ARG(!sb8 && !pool, "layout flags");
-        SLR_CHECK_ARG(sk->w && a.Cout <= CF_MAXCO && (layout & SLR_CONV_IN_B8) && !((uintptr_t)sk->w & 15),
+        SLR_CHECK_ARG_FN(fn, !sb8 && !pool, "layout flags");
+        SLR_CHECK_ARG_FN(fn, sk->w && a.Cout <= CF_MAXCO && (layout & SLR_CONV_IN_B8) && !((uintptr_t)sk->w & 15),
                       "the skip output needs Cout <= 4, a channel-blocked input and 16-byte aligned [Cin][4] weights");
-        SLR_CHECK_ARG(a.pre != PRE_BN_NONZERO, "the skip output goes with an explicit mask");
+        SLR_CHECK_ARG_FN(fn, a.pre != PRE_BN_NONZERO, "the skip output goes with an explicit mask");
         a.skip_w = (const h8 *)sk->w; a.skip_bias = sk->bias; a.skip_out = sk->skip_out;
         return 0;
     }
-    SLR_CHECK_ARG(sk->in && sk->w, "null pointer");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_WINO), "no fused skip branch in the Winograd kernel");
-    SLR_CHECK_ARG(!(layout & SLR_CONV_F32) || (conv_cout_tile(a.Cout) == 128 && sk->wscale == 1.0f),
+    SLR_CHECK_ARG_FN(fn, sk->in && sk->w, "null pointer");
+    SLR_CHECK_ARG_FN(fn, !(layout & SLR_CONV_WINO), "no fused skip branch in the Winograd kernel");
+    SLR_CHECK_ARG_FN(fn, !(layout & SLR_CONV_F32) || (conv_cout_tile(a.Cout) == 128 && sk->wscale == 1.0f),
                   "the fused skip branch on the fp32 rung: more than 64 output channels, skip_wscale = 1");
-    SLR_CHECK_ARG((layout & SLR_CONV_IN_B8) && a.Cout > CF_MAXCO, "the fused skip branch needs a channel-blocked main input and more than 4 output channels");
-    SLR_CHECK_ARG(sk->cin > 0 && (long long)sk->cin * a.H * a.W < (1LL << 31) && sk->wscale > 0.0f, "skip sizes");
-    SLR_CHECK_ARG(sb8 && sk->cin % 8 == 0 && !((uintptr_t)sk->in & 15), "the fused skip branch reads a channel-blocked skip input (SLR_CONV_SKIP_B8): skip_cin % 8 == 0, 16-byte aligned");
-    SLR_CHECK_ARG(!a.residual && !a.next_scale, "the fused skip branch replaces the residual; no next-BN fusion with it");
+    SLR_CHECK_ARG_FN(fn, (layout & SLR_CONV_IN_B8) && a.Cout > CF_MAXCO, "the fused skip branch needs a channel-blocked main input and more than 4 output channels");
+    SLR_CHECK_ARG_FN(fn, sk->cin > 0 && (long long)sk->cin * a.H * a.W < (1LL << 31) && sk->wscale > 0.0f, "skip sizes");
+    SLR_CHECK_ARG_FN(fn, sb8 && sk->cin % 8 == 0 && !((uintptr_t)sk->in & 15), "the fused skip branch reads a channel-blocked skip input (SLR_CONV_SKIP_B8): skip_cin % 8 == 0, 16-byte aligned");
+    SLR_CHECK_ARG_FN(fn, !a.residual && !a.next_scale, "the fused skip branch replaces the residual; no next-BN fusion with it");
     a.skip_in = sk->in; a.skip_w = (const h8 *)sk->w; a.skip_bias = sk->bias;
     a.skip_cin = sk->cin; a.skip_nchunk = conv_cin_pad(sk->cin) / 16;
     a.skip_unscale = 1.0f / (xscale * sk->wscale);
     if (pool) {
-        SLR_CHECK_ARG(!(up && (layout_in & SLR_CONV_POOL_OUT)), "SLR_CONV_POOL_OUT and SLR_CONV_UP_OUT are exclusive");
-        SLR_CHECK_ARG(a.out_b8 && conv_cout_tile(a.Cout) == 128, "the resampling epilogues need a channel-blocked output and more than 64 output channels");
-        SLR_CHECK_ARG(!up || (long long)a.N * a.Cout * a.H * a.W < (1LL << 38), "sizes");
-        SLR_CHECK_ARG(sk->pool_ws && !((uintptr_t)sk->pool_ws & 15) && sk->pool_ws_bytes >= conv_pool_ws_bytes(a.N, a.Cout, a.H, a.W, up),
+        SLR_CHECK_ARG_FN(fn, !(up && (layout_in & SLR_CONV_POOL_OUT)), "SLR_CONV_POOL_OUT and SLR_CONV_UP_OUT are exclusive");
+        SLR_CHECK_ARG_FN(fn, a.out_b8 && conv_cout_tile(a.Cout) == 128, "the resampling epilogues need a channel-blocked output and more than 64 output channels");
+        SLR_CHECK_ARG_FN(fn, !up || (long long)a.N * a.Cout * a.H * a.W < (1LL << 38), "sizes");
+        SLR_CHECK_ARG_FN(fn, (long long)a.N * (a.Cout >> 3) <= 65535, "sizes (the resampling epilogues: N * Cout / 8 <= 65535)");
+        SLR_CHECK_ARG_FN(fn, sk->pool_ws && !((uintptr_t)sk->pool_ws & 15) && sk->pool_ws_bytes >= conv_pool_ws_bytes(a.N, a.Cout, a.H, a.W, up),
                       "pool_ws: slr_conv_pool_ws_bytes / slr_conv_up_ws_bytes, 16-byte aligned");
         a.tiles_y = (a.H + CV_H - 1) / CV_H;
         a.resample = up ? 2 : 1;
@@ -1774,13 +1777,13 @@ static constexpr bool conv_split_built() {
            !(F32 && SKIP && WCO != 4);
 }
 
-static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipStream_t st, bool tail = false) {
+static int conv_launch(const char *fn, ConvArgs &a, float wscale, float xscale, int layout, hipStream_t st, bool tail = false) {
     const bool in_b8 = (layout & SLR_CONV_IN_B8) != 0, f32 = (layout & SLR_CONV_F32) != 0, wino = (layout & SLR_CONV_WINO) != 0;
     const bool pre = a.pre != PRE_NONE;
-    if (int e = check_xscale(xscale)) return e;
-    SLR_CHECK_ARG(!f32 || (wscale == 1.0f && xscale == 1.0f), "the fp32 rung takes no operand scales (wscale = xscale = 1)");
-    SLR_CHECK_ARG(!wino || (f32 && a.Cout > CF_MAXCO), "SLR_CONV_WINO goes with SLR_CONV_F32 and more than 4 output channels");
-    SLR_CHECK_ARG(!wino || !pre || a.Cin <= WN_MAXCIN, "SLR_CONV_WINO with a prologue supports Cin <= 256");
+    if (int e = check_xscale(fn, xscale)) return e;
+    SLR_CHECK_ARG_FN(fn, !f32 || (wscale == 1.0f && xscale == 1.0f), "the fp32 rung takes no operand scales (wscale = xscale = 1)");
+    SLR_CHECK_ARG_FN(fn, !wino || (f32 && a.Cout > CF_MAXCO), "SLR_CONV_WINO goes with SLR_CONV_F32 and more than 4 output channels");
+    SLR_CHECK_ARG_FN(fn, !wino || !pre || a.Cin <= WN_MAXCIN, "SLR_CONV_WINO with a prologue supports Cin <= 256");
     if (wino) {
         a.tiles_x = (a.W + WN_BW - 1) / WN_BW;
         a.nchunk = conv_cin_pad(a.Cin) / 16;
@@ -1797,7 +1800,7 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
                 hipLaunchKernelGGL((conv3x3_wino_kernel<pre_, b8>), grid, dim3(WN_THREADS), WN_LDS_BYTES, st, a);
                 return 0;
             }, pre, in_b8)) return e;
-        SLR_CHECK_LAUNCH();
+        SLR_CHECK_HIP_FN(fn, hipGetLastError());
         return 0;
     }
     if (a.Cout <= CF_MAXCO) {                           // fp32 FMAs on the vector ALUs on either rung: no operand scales, nothing saturates
@@ -1809,7 +1812,7 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
                     return 0;
                 }, pre, in_b8, a.skip_out != nullptr);
             })) return e;
-        SLR_CHECK_LAUNCH();
+        SLR_CHECK_HIP_FN(fn, hipGetLastError());
         return 0;
     }
     a.tiles_x = (a.W + CV_W - 1) / CV_W;
@@ -1824,7 +1827,7 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
     if (tail) {                                         // (slr_pconv3x3_forward_tail has checked what the one instantiation needs)
         hipLaunchKernelGGL((conv3x3_split_kernel<1, 4, false, true, false, false, false, false, true>),
                            dim3(a.tiles_x * ((a.H + CV_H - 1) / CV_H), 1, a.N), dim3(CV_THREADS), 0, st, a);
-        SLR_CHECK_LAUNCH();
+        SLR_CHECK_HIP_FN(fn, hipGetLastError());
         return 0;
     }
     int ct = conv_cout_tile(a.Cout);
@@ -1838,19 +1841,19 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
                 return 0;
             }, pre, in_b8, f32, a.skip_in != nullptr, a.resample == 1, a.resample == 2);
         })) return e;
-    SLR_CHECK_LAUNCH();
+    SLR_CHECK_HIP_FN(fn, hipGetLastError());
     if (a.resample == 2) {                              // the up-sampling epilogue's tile borders
         const int items = 2 * a.tiles_y * 2 * a.W + 2 * a.tiles_x * 2 * a.H;
         hipLaunchKernelGGL(upsample_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
                            (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
-        SLR_CHECK_LAUNCH();
+        SLR_CHECK_HIP_FN(fn, hipGetLastError());
     } else if (a.resample == 1) {                       // ... the pooling epilogue's
         const int OH = (a.H - 1) / 2 + 1, OW = (a.W - 1) / 2 + 1;
         const int items = (a.tiles_y - 1) * OW + (a.tiles_x - 1) * OH;
         if (items > 0) {
             hipLaunchKernelGGL(pool_fix_kernel, dim3((items + 255) / 256, a.N * (a.Cout >> 3)), dim3(256), 0, st, a.out, (const float *)a.pool_row,
                                (const float *)a.pool_col, a.Cout >> 3, a.H, a.W, a.tiles_x, a.tiles_y);
-            SLR_CHECK_LAUNCH();
+            SLR_CHECK_HIP_FN(fn, hipGetLastError());
         }
     }
     return 0;
@@ -1858,18 +1861,18 @@ static int conv_launch(ConvArgs &a, float wscale, float xscale, int layout, hipS
 
 // ConvArgs of the six 3x3 entry points.  partial: the partial convolution (bias required; mask == NULL: derived from x != 0, needs the
 // prologue); the plain one passes no mask, next-BN or update mask.  sk: the fused skip branch or the skip output, or NULL.
-static int conv3x3_run(bool partial, const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
+static int conv3x3_run(const char *fn, bool partial, const float *x, const float *pre_scale, const float *pre_shift, const float *mask,
                        const void *wsplit, float wscale, float xscale, const float *bias, const float *residual,
                        const float *next_scale, const float *next_shift, float *out, float *um_out,
                        int N, int Cin, int Cout, int H, int W, const SkipOp *sk, int layout, void *stream) {
-    SLR_CHECK_ARG(x && wsplit && (bias || !partial) && out, "null pointer");
-    if (int e = conv_check_layout(layout, x, out, Cin, Cout, residual, partial && !mask)) return e;
-    SLR_CHECK_ARG(!pre_scale == !pre_shift, "pre_scale / pre_shift go together");
-    SLR_CHECK_ARG(!pre_scale || Cin <= CV_MAXCIN, "prologue supports Cin <= 1024");
-    SLR_CHECK_ARG(!partial || mask || pre_scale, "mask = NULL (derived from x != 0) needs the raw input, i.e. pre_scale / pre_shift");
-    SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
-    SLR_CHECK_ARG(!(residual && next_scale), "residual and next-BN fusion are exclusive");
-    if (int e = conv_check_dims(N, Cin, Cout, H, W)) return e;
+    SLR_CHECK_ARG_FN(fn, x && wsplit && (bias || !partial) && out, "null pointer");
+    if (int e = conv_check_layout(fn, layout, x, out, Cin, Cout, residual, partial && !mask)) return e;
+    SLR_CHECK_ARG_FN(fn, !pre_scale == !pre_shift, "pre_scale / pre_shift go together");
+    SLR_CHECK_ARG_FN(fn, !pre_scale || Cin <= CV_MAXCIN, "prologue supports Cin <= 1024");
+    SLR_CHECK_ARG_FN(fn, !partial || mask || pre_scale, "mask = NULL (derived from x != 0) needs the raw input, i.e. pre_scale / pre_shift");
+    SLR_CHECK_ARG_FN(fn, !next_scale == !next_shift, "next_scale / next_shift go together");
+    SLR_CHECK_ARG_FN(fn, !(residual && next_scale), "residual and next-BN fusion are exclusive");
+    if (int e = conv_check_dims(fn, N, Cin, Cout, H, W)) return e;
     ConvArgs a = {};
     a.in = x; a.w = (const h8 *)wsplit; a.bias = bias; a.out = out;
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
@@ -1883,14 +1886,14 @@ static int conv3x3_run(bool partial, const float *x, const float *pre_scale, con
     a.residual = residual; a.next_scale = next_scale; a.next_shift = next_shift; a.um_out = um_out;
     a.out_b8 = (layout & SLR_CONV_OUT_B8) != 0;
     a.res_b8 = (layout & SLR_CONV_RES_B8) != 0;
-    if (int e = conv_set_skip(a, sk, xscale, layout)) return e;
-    return conv_launch(a, wscale, xscale, layout, (hipStream_t)stream);
+    if (int e = conv_set_skip(fn, a, sk, xscale, layout)) return e;
+    return conv_launch(fn, a, wscale, xscale, layout, (hipStream_t)stream);
 }
 
 SLR_EXPORT int slr_conv3x3_forward(const float *in, const void *wsplit, const float *bias, const float *residual,
                                    float *out, int N, int Cin, int Cout, int H, int W, float wscale, float xscale,
                                    const float *pre_scale, const float *pre_shift, int layout, void *stream) {
-    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
+    return conv3x3_run(__func__, false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
                        N, Cin, Cout, H, W, nullptr, layout, stream);
 }
 
@@ -1900,7 +1903,7 @@ SLR_EXPORT int slr_conv3x3_forward_skip(const float *in, const void *wsplit, con
                                         const float *skip_in, const void *skip_wsplit, const float *skip_bias, int skip_cin, float skip_wscale,
                                         void *pool_ws, size_t pool_ws_bytes, int layout, void *stream) {
     const SkipOp sk = {skip_in, skip_wsplit, skip_bias, skip_cin, skip_wscale, pool_ws, pool_ws_bytes, nullptr};
-    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, nullptr,
+    return conv3x3_run(__func__, false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, nullptr,
                        N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
@@ -1910,7 +1913,7 @@ SLR_EXPORT int slr_conv3x3_forward_skipout(const float *in, const void *wsplit, 
                                            const float *skip_w4, const float *skip_bias, float *skip_out, int layout, void *stream) {
     SLR_CHECK_ARG(skip_w4 && skip_out, "null pointer");
     const SkipOp sk = {nullptr, skip_w4, skip_bias, 0, 1.0f, nullptr, 0, skip_out};
-    return conv3x3_run(false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
+    return conv3x3_run(__func__, false, in, pre_scale, pre_shift, nullptr, wsplit, wscale, xscale, bias, residual, nullptr, nullptr, out, nullptr,
                        N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
@@ -1918,7 +1921,7 @@ SLR_EXPORT int slr_pconv3x3_forward(const float *x, const float *pre_scale, cons
                                     const void *wsplit, float wscale, float xscale, const float *bias, const float *residual,
                                     const float *next_scale, const float *next_shift, float *out, float *um_out,
                                     int N, int Cin, int Cout, int H, int W, int layout, void *stream) {
-    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
+    return conv3x3_run(__func__, true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
                        N, Cin, Cout, H, W, nullptr, layout, stream);
 }
 
@@ -1928,7 +1931,7 @@ SLR_EXPORT int slr_pconv3x3_forward_skip(const float *x, const float *pre_scale,
                                          const float *skip_in, const void *skip_wsplit, int skip_cin, float skip_wscale,
                                          void *pool_ws, size_t pool_ws_bytes, int layout, void *stream) {
     const SkipOp sk = {skip_in, skip_wsplit, nullptr, skip_cin, skip_wscale, pool_ws, pool_ws_bytes, nullptr};
-    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, um_out,
+    return conv3x3_run(__func__, true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, nullptr, nullptr, nullptr, out, um_out,
                        N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
@@ -1939,7 +1942,7 @@ SLR_EXPORT int slr_pconv3x3_forward_skipout(const float *x, const float *pre_sca
                                             const float *skip_w4, float *skip_out, int layout, void *stream) {
     SLR_CHECK_ARG(skip_w4 && skip_out, "null pointer");
     const SkipOp sk = {nullptr, skip_w4, nullptr, 0, 1.0f, nullptr, 0, skip_out};
-    return conv3x3_run(true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
+    return conv3x3_run(__func__, true, x, pre_scale, pre_shift, mask, wsplit, wscale, xscale, bias, residual, next_scale, next_shift, out, um_out,
                        N, Cin, Cout, H, W, &sk, layout, stream);
 }
 
@@ -1973,7 +1976,7 @@ SLR_EXPORT int slr_pconv3x3_forward_tail(const float *x, const float *mask, cons
                                          float *z_out, float *um_out, int N, int Cin, int Cout, int H, int W, void *stream) {
     SLR_CHECK_ARG(x && mask && wsplit && bias && tail_scale && tail_shift && wtail && z_out, "null pointer");
     SLR_CHECK_ARG(Cout == 128, "the tail phase is built for 128 output channels");
-    if (int e = conv_check_dims(N, Cin, Cout, H, W)) return e;
+    if (int e = conv_check_dims(__func__, N, Cin, Cout, H, W)) return e;
     SLR_CHECK_ARG(Cin % 8 == 0 && !(((uintptr_t)x | (uintptr_t)residual | (uintptr_t)wtail) & 15),
                   "channel-blocked input and residual: Cin % 8 == 0, 16-byte aligned tensors and tail weights");
     SLR_CHECK_ARG(!((uintptr_t)z_out & 3), "4-byte aligned Z");
@@ -1987,7 +1990,7 @@ SLR_EXPORT int slr_pconv3x3_forward_tail(const float *x, const float *mask, cons
     a.residual = residual; a.next_scale = tail_scale; a.next_shift = tail_shift; a.um_out = um_out;
     a.out_b8 = 1; a.res_b8 = 1;
     a.skip_w = (const h8 *)wtail;
-    return conv_launch(a, wscale, xscale, SLR_CONV_IN_B8, (hipStream_t)stream, true);
+    return conv_launch(__func__, a, wscale, xscale, SLR_CONV_IN_B8, (hipStream_t)stream, true);
 }
 
 SLR_EXPORT int slr_narrow_gather(const float *z, const float *mask, const float *bias, const float *next_scale, const float *next_shift,
@@ -1995,9 +1998,9 @@ SLR_EXPORT int slr_narrow_gather(const float *z, const float *mask, const float 
                                  float wscale, float skip_wscale, float xscale, void *stream) {
     SLR_CHECK_ARG(z && mask && bias && out && um_out && skip_out, "null pointer");
     SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
-    if (int e = check_xscale(xscale)) return e;
+    if (int e = check_xscale(__func__, xscale)) return e;
     SLR_CHECK_ARG(wscale > 0.0f && skip_wscale > 0.0f, "wscale");
-    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && (H + 3) / 4 < 65536, "sizes");
+    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) - 64 && (H + 3) / 4 < 65536, "sizes");
     hipLaunchKernelGGL(narrow_gather_kernel, dim3((W + 63) / 64, (H + 3) / 4, N), dim3(256), 0, (hipStream_t)stream, z, mask, bias, next_scale,
                        next_shift, skip_bias, out, um_out, skip_out, H, W, (float)Cin, (float)Cin * 9.0f, 1.0f / (xscale * wscale),
                        1.0f / (xscale * skip_wscale));

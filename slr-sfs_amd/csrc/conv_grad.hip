@@ -273,7 +273,8 @@ static int wg_splits(int N, int Cin, int Cout, int H, int W, int splits) {
 }
 static bool wg_sizes_ok(int N, int Cin, int Cout, int H, int W) {
     return N > 0 && Cin >= 0 && Cout > 0 && H > 0 && W > 0 && Cin <= 65535 * 64 && Cout <= 65535 * 64 &&
-           (long long)N * (Cin > Cout ? Cin : Cout) * H * W < (1LL << 31) && (long long)N * Cout <= 65535;
+           (long long)N * (Cin > Cout ? Cin : Cout) * H * W < (1LL << 31) - 4 * WG_THREADS && (long long)N * Cout <= 65535 &&
+           9LL * Cout * Cin < (1LL << 31) - 64;     // (a thread's first pixel, rounded up to a workgroup of 4-pixel items, and the sum kernel's element stay an int)
 }
 
 static int wg_scale_bias(const float *g, const float *r, const float *um, float *gr, float *db, int N, int C, int H, int W, int b8,
@@ -308,7 +309,7 @@ SLR_EXPORT size_t slr_conv3x3_grad_ws_bytes(int N, int Cin, int Cout, int H, int
 SLR_EXPORT int slr_conv3x3_weight_grad(const float *x, const float *g, float *dw, float *db, int N, int Cin, int Cout, int H, int W,
                                        int splits, int layout, void *ws, size_t ws_bytes, void *stream) {
     SLR_CHECK_ARG(x && g && dw, "null pointer");
-    SLR_CHECK_ARG(Cin > 0 && wg_sizes_ok(N, Cin, Cout, H, W), "sizes (N * max(Cin, Cout) * H * W < 2^31, N * Cout <= 65535)");
+    SLR_CHECK_ARG(Cin > 0 && wg_sizes_ok(N, Cin, Cout, H, W), "sizes (N * max(Cin, Cout) * H * W < 2^31 - 1024, N * Cout <= 65535, 9 * Cout * Cin < 2^31 - 64)");
     SLR_CHECK_ARG(splits >= 0, "splits (0 = chosen by the library)");
     SLR_CHECK_ARG(!(layout & ~(SLR_GRAD_X_B8 | SLR_GRAD_G_B8)), "layout");
     const bool xb8 = layout & SLR_GRAD_X_B8, gb8 = layout & SLR_GRAD_G_B8;
@@ -349,7 +350,7 @@ SLR_EXPORT int slr_conv_grad_scale_bias(const float *g, const float *r, const fl
                                         int layout, void *ws, size_t ws_bytes, void *stream) {
     SLR_CHECK_ARG(g && (gr || db), "null pointer");
     SLR_CHECK_ARG(!gr || r, "null pointer: gr needs r");
-    SLR_CHECK_ARG(wg_sizes_ok(N, 0, C, H, W), "sizes (N * C * H * W < 2^31, N * C <= 65535)");
+    SLR_CHECK_ARG(wg_sizes_ok(N, 0, C, H, W), "sizes (N * C * H * W < 2^31 - 1024, N * C <= 65535)");
     SLR_CHECK_ARG(!(layout & ~SLR_GRAD_G_B8), "layout");
     const bool b8 = layout & SLR_GRAD_G_B8;
     SLR_CHECK_ARG(!b8 || C % 8 == 0, "SLR_GRAD_G_B8 needs C % 8 == 0");

@@ -193,7 +193,8 @@ SLR_EXPORT int slr_euler_backward_batch(const float *motion, const long long *st
                                         const float *grad_disp, float *grad_motion, void *stream) {
     SLR_CHECK_ARG(motion && steps && grad_disp && grad_motion, "null pointer");
     SLR_CHECK_ARG(B > 0 && B < 65536 && H > 0 && W > 0, "sizes");
-    SLR_CHECK_ARG((long long)H * W < (1LL << 30) && (long long)B * H * W < (1LL << 40), "sizes too large");
+    // (the zero kernel's grid, ceil(2 B H W / 256) workgroups, stays below 2^31)
+    SLR_CHECK_ARG((long long)H * W < (1LL << 30) && (long long)B * H * W < (1LL << 38) - 128, "sizes too large");
     SLR_CHECK_ARG(sign == 1.0f || sign == -1.0f, "sign must be +1 or -1");
     const int blocks = (H * W + 255) / 256;
     const size_t n = (size_t)B * 2 * H * W;

@@ -276,8 +276,8 @@ SLR_EXPORT size_t slr_ssim_ws_bytes(int N, int H, int W) {
 SLR_EXPORT int slr_ssim_mse(const void *img1, const void *img2, int u8, const float *mask, float *out, int N, int C, int H, int W,
                             int window_size, void *ws, size_t ws_bytes, void *stream) {
     SLR_CHECK_ARG(img1 && img2 && out && ws, "null pointer");
-    SLR_CHECK_ARG(N > 0 && N < 65536 && C > 0 && C <= 64 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) &&
-                  (long long)N * C * H * W < (1LL << 40), "sizes");
+    SLR_CHECK_ARG(N > 0 && N < 65536 && C > 0 && C <= 64 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) - 2 * SS_TW &&
+                  (long long)N * C * H * W < (1LL << 40), "sizes");      // (a column past the last tile's halo stays an int)
     SLR_CHECK_ARG(window_size >= 1 && window_size <= 2 * SS_RMAX + 1 && window_size % 2 == 1, "window_size: odd, 1 .. 15");
     SLR_CHECK_ARG(ws_bytes >= slr_ssim_ws_bytes(N, H, W) && !((uintptr_t)ws & 7), "ws: slr_ssim_ws_bytes(N, H, W), 8-byte aligned");
     SsimArgs a = {};

@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256) void resize_segmap_kernel(const float *__restr
 
 SLR_EXPORT int slr_resize_segmap(const float *in, float *out, int N, int C, int H, int W, int k, int nearest_channel, void *stream) {
     SLR_CHECK_ARG(in && out, "null pointer");
-    SLR_CHECK_ARG(N > 0 && C > 0 && k >= 0 && k < 16 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && (long long)N * C < 65536,
-                  "sizes");
+    SLR_CHECK_ARG(N > 0 && C > 0 && k >= 0 && k < 16 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) - 256 && (long long)N * C < 65536,
+                  "sizes");      // (k = 0: a work-item's pixel, rounded up to the workgroup, stays an int)
     SLR_CHECK_ARG(H % (1 << k) == 0 && W % (1 << k) == 0, "H and W must be multiples of 2^k");
     const int OHW = (H >> k) * (W >> k);
     hipLaunchKernelGGL(resize_segmap_kernel, dim3((OHW + 255) / 256, N * C), dim3(256), 0, (hipStream_t)stream, in, out, C, H, W, k,
@@ -156,7 +156,8 @@ SLR_EXPORT int slr_upsample2x_concat(const float *a, int Ca, const float *b, int
                                      int nearest_channel, int relu, void *stream) {
     SLR_CHECK_ARG(a && out && (Cb == 0 || b), "null pointer");
     SLR_CHECK_ARG(relu >= 0 && relu <= 2, "relu: 0 none, 1 before, 2 after the up-sampling");
-    SLR_CHECK_ARG(N > 0 && Ca > 0 && Cb >= 0 && H > 0 && W > 0 && (long long)N * (Ca + Cb) < 65536 && 4LL * H * W < (1LL << 31), "sizes");
+    SLR_CHECK_ARG(N > 0 && Ca > 0 && Cb >= 0 && H > 0 && W > 0 && (long long)N * (Ca + Cb) < 65536 && 4LL * H * W < (1LL << 31) - 256,
+                  "sizes");                                       // (an output pixel's index, rounded up to the workgroup, stays an int)
     hipLaunchKernelGGL(upsample2x_concat_kernel, dim3((4 * H * W + 255) / 256, N * (Ca + Cb)), dim3(256), 0, (hipStream_t)stream, a, Ca,
                        b, Cb, out, H, W, nearest_channel, relu);
     SLR_CHECK_LAUNCH();

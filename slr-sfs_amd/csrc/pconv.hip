@@ -95,10 +95,14 @@ __global__ __launch_bounds__(256) void pconv_epilogue_kernel(const V *__restrict
     }
 }
 
+// Workgroups along a plane, at most: the kernels' loops step by gridDim.x * 256, so the entry points keep H * W below 2^31 minus one
+// such step (the index of the step that leaves the loop stays an int).
+constexpr int PL_MAX_BX = 1024;
+
 template <typename V, typename F>
 static void launch_planes(F f, int N, int C, int HWv, hipStream_t st) {
     int bx = (HWv + 255) / 256;
-    if (bx > 1024) bx = 1024;
+    if (bx > PL_MAX_BX) bx = PL_MAX_BX;
     f(dim3(bx, C, N), st);
 }
 
@@ -110,7 +114,7 @@ SLR_EXPORT int slr_bn_relu_mask(const float *x, const float *scale, const float 
                                 int mask_channels, float *y, int N, int C, int H, int W, void *stream) {
     SLR_CHECK_ARG(x && scale && shift && y, "null pointer");
     SLR_CHECK_ARG(mask_channels == 0 || mask_channels == -1 || (mask && (mask_channels == 1 || mask_channels == C)), "mask");
-    SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && N <= 65535, "sizes");
+    SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && N <= 65535 && (long long)H * W < (1LL << 31) - PL_MAX_BX * 256, "sizes");
     hipStream_t st = (hipStream_t)stream;
     const int HW = H * W;
     const bool v4 = (HW % 4 == 0) && !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)mask) & 15);
@@ -135,7 +139,7 @@ SLR_EXPORT int slr_pconv_epilogue(const float *raw0, const float *bias, const fl
     SLR_CHECK_ARG(raw0 && bias && um_raw && out, "null pointer");
     SLR_CHECK_ARG(!next_scale == !next_shift, "next_scale / next_shift go together");
     SLR_CHECK_ARG(!(residual && next_scale), "residual and next-BN fusion are exclusive");
-    SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && N <= 65535, "sizes");
+    SLR_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && C <= 65535 && N <= 65535 && (long long)H * W < (1LL << 31) - PL_MAX_BX * 256, "sizes");
     hipStream_t st = (hipStream_t)stream;
     const int HW = H * W;
     const bool v4 = (HW % 4 == 0) && !(((uintptr_t)raw0 | (uintptr_t)out | (uintptr_t)um_raw | (uintptr_t)residual | (uintptr_t)um_out) & 15);

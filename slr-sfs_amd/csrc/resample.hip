@@ -272,7 +272,9 @@ SLR_EXPORT int slr_conv1x1_small(const float *in, const float *w, const float *b
                                  int Cout, int H, int W, int in_b8, void *stream) {
     SLR_CHECK_ARG(in && w && out, "null pointer");
     SLR_CHECK_ARG(Cout >= 1 && Cout <= 4, "1 <= Cout <= 4");
-    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && H > 0 && W > 0, "sizes");
+    // (a work-item's pixel, rounded up to the workgroup, and the weight index co * Cin + ci stay an int)
+    SLR_CHECK_ARG(N > 0 && N < 65536 && Cin > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 31) - 256 &&
+                  (long long)Cout * Cin < (1LL << 31), "sizes");
     if (in_b8) {
         SLR_CHECK_ARG(Cin % 8 == 0 && !((uintptr_t)in & 15), "channel-blocked input needs Cin % 8 == 0 and a 16-byte aligned tensor");
         const dim3 g8((H * W + 255) / 256, N);
